@@ -12,9 +12,16 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JS
                     (what a literal "W warm-up steps from scratch, then K steps" measures: 15-25x more samples
                     per ray than the steady state, plus first-touch costs);
                 (2) W untimed warm-up steps;
-                (3) K timed steps bracketed by barrier + synchronize on both sides, max over ranks; the window
+                (3) K timed steps bracketed by barrier + synchronize on both sides, max over ranks; `value` is
+                    rays over the window time and `ms_per_step` the window time / K.  With `--full` the window
                     is repeated until >= MIN_TIMED_STEPS (200) steps are covered and `value` is rays over the
                     summed window time (`timed_windows`, `timed_steps_total` say how many).
+  * plain run = setup, warm-up, the K timed steps, `--dump-outputs DIR` if given, the line -- nothing else.  Every leg
+                below, the cold-start window, the exchange timing, the host accounting and the march-guard readout run
+                with `--full` only.
+  * --dump-outputs DIR = what the last timed step computed, as float32/float64 .npy files (DUMP_LIMIT bytes at most):
+                that step's per-ray colour / opacity / sample counts and loss sums, and the parameters the step's Adam left.
+                The inputs are seeded: the same arguments give the same inputs run after run.
   * value     = rays/s over all ranks (weak scaling: 8192 rays per GPU) of `Trainer.step`, the native step
                 (direct C-ABI calls, no autograd graph).  `api_path` is the same step driven through the
                 reference-shaped surface (render() + NeRFLoss + autograd + FusedAdam).
@@ -32,7 +39,7 @@ gradient exchange per step (ngp_pl_amd/ddp.py) -- the reference's only collectiv
 Without a GPU (`--dry-run`, implied when none is visible) only the launcher and the process group are
 exercised (gloo): the product path has no CPU fallback.
 
-Legs behind the headline (each with its own budget; the line is printed with whatever is complete): under a process group, on every
+Legs behind the headline (`--full` only; each with its own budget; the line is printed with whatever is complete): under a process group, on every
 rank, `dp_eval` (more data-parallel steps, then the evaluation sharded over the ranks, train.py:193-237) and `exchange_modes` (the other
 exchange modes on the same communicator); then on rank 0 `roofline`, `cpu_baseline`, `full_run`, the FPS legs (incl.
 `render_fps_800x800_reference_files`: test.ipynb cell 2 around the reference's own rendering.py on the bindings), `api_path`,
@@ -68,6 +75,7 @@ sys.path.insert(0, ROOT)
 SETUP_STEPS = 320          # untimed, disclosed (>= 300 steps, past the 256-step occupancy warm-up)
 MIN_TIMED_STEPS = 200
 ROOFLINE_STEPS = 20
+DUMP_LIMIT = 64 * 2 ** 20  # bytes of --dump-outputs, all files together
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 achievable
 WORKLOADS = {
     # name: (scene, scale, rays, lr, erode, description)
@@ -105,6 +113,10 @@ def parse():
     p.add_argument("--no-full-run", action="store_true", help="skip the literal configs[1] run (30 000 steps from scratch + evaluation over 200 held-out poses, ~15 s)")
     p.add_argument("--timed-only", action="store_true", help="stop after the timed windows (for rocprofv3 runs: the trace then ends with the timed steps)")
     p.add_argument("--dry-run", action="store_true", help="launcher + process group only (gloo, no GPU work)")
+    p.add_argument("--full", action="store_true", help="everything behind the headline as well: timed windows up to 200 steps, cold start, "
+                   "roofline, CPU baseline, full run, FPS legs, api paths, other recipes, sensitivity, exchange legs (the --no-* options "
+                   "drop single legs of it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -312,12 +324,17 @@ class Loop:
             modes["switch_back_error"] = "%s: %s" % (type(e).__name__, str(e)[:200])
         return modes
 
-    def run(self, setup_steps, warmup, steps, min_timed=MIN_TIMED_STEPS):
-        """setup (with the cold-start window inside) -> warm-up -> timed windows.  Returns the result record."""
+    def run(self, setup_steps, warmup, steps, min_timed=MIN_TIMED_STEPS, full=True, dump=None):
+        """setup (with the cold-start window inside) -> warm-up -> timed windows.  Returns the result record.  full=False: no cold-start
+        window, ONE timed window of `steps` steps, no exchange timing or host accounting.  `dump`: directory for dump_outputs(), written
+        right behind the timed windows (rank 0)."""
         tr = self.trainer
         cold = None
         w0 = min(warmup, max(setup_steps - steps, 0))
-        if setup_steps >= w0 + steps:
+        if not full:
+            min_timed = steps
+            self.steps(setup_steps)
+        elif setup_steps >= w0 + steps:
             self.steps(w0)
             dt, _ = self.timed(steps)
             met = tr.metrics()
@@ -329,7 +346,7 @@ class Loop:
         else:
             self.steps(setup_steps)
         self.steps(warmup)
-        if hasattr(tr, "host_times"):
+        if full and hasattr(tr, "host_times"):
             tr.host_times(reset=True)              # host accounting of the native stepper: the timed windows only
         n_win = max(1, -(-min_timed // steps))
         wins, ev = [], []
@@ -337,18 +354,45 @@ class Loop:
             dt, dte = self.timed(steps)
             wins.append(dt); ev.append(dte)
         total = sum(wins)
+        if dump and self.rank == 0:
+            dump_outputs(self, dump)
         met = tr.metrics()
         extra = {}
-        host = tr.host_times(reset=True) if hasattr(tr, "host_times") else None
+        host = tr.host_times(reset=True) if full and hasattr(tr, "host_times") else None
         if host:                       # native stepper only: polling for the march's count (device-bound) vs launches / events / checks
             extra["host_ms_per_step"] = host
-        if self.exchange is not None:          # the exchange stage on its own: 20 more steps with device events around it (all ranks alike)
+        if full and self.exchange is not None:          # the exchange stage on its own: 20 more steps with device events around it (all ranks alike)
             extra.update({"exchange": self.exchange_kind, "exchange_impl": self.exchange_impl})
             extra.update(self.time_exchange())
         return {**extra, "ms_per_step": total / (n_win * steps) * 1e3, "rays_per_s": self.rays * self.world * n_win * steps / total,
                 "timed_windows": n_win, "timed_steps_total": n_win * steps, "window_ms_per_step_min_max": [min(wins) / steps * 1e3, max(wins) / steps * 1e3],
                 "ms_per_step_hip_events": sum(ev) / (n_win * steps) * 1e3, "cold_start": cold, "metrics": met,
                 "global_step_at_end": tr.global_step}
+
+
+def dump_outputs(loop, out_dir, limit=DUMP_LIMIT):
+    """What `Trainer.step` handed back for the last step (its record: per-ray rgb / opacity / composited sample counts, the loss sums)
+    and the parameters that step's Adam left, as DIR/<name>.npy in float32 (float64 for the integer counts).  A parameter vector that
+    does not fit in what is left of `limit` is written as a fixed sample (seed 0, sorted positions) under <name>_sample."""
+    import numpy as np
+    torch.cuda.synchronize()
+    last, m = loop.trainer.last, loop.model
+    arrays = [("rgb", last["rgb"].float()), ("opacity", last["opacity"].float()), ("total_samples", last["total"].double()),
+              ("loss_sums", last["stats"].float()),
+              ("samples", torch.tensor([float(last["rm_samples"]), float(last["n_active"].item())], dtype=torch.float64)),
+              ("rgb_net_params", m.rgb_net.params.detach().float()), ("xyz_encoder_params", m.xyz_encoder.params.detach().float())]
+    os.makedirs(out_dir, exist_ok=True)
+    left = limit
+    for name, t in arrays:
+        t = t.reshape(-1) if name.endswith("_params") else t
+        if t.numel() * t.element_size() + 128 > left:
+            k = max((left - 128) // t.element_size(), 0)
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            t, name = t[idx.to(t.device)], name + "_sample"
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes + 128                 # (an .npy header is 128 bytes)
+    return out_dir
 
 
 def kernel_roofline(loop, ms_per_step=None, n_steps=ROOFLINE_STEPS):
@@ -1169,7 +1213,7 @@ def main():
     keeper.phase("dataset + model (%s)" % args.workload, 90.0)
     loop = Loop(args.workload, args, dev, rank, world, dist)
     keeper.phase("setup %d steps + warm-up %d + timed windows of %d" % (args.setup_steps, args.warmup, args.steps), 120.0)
-    r = loop.run(args.setup_steps, args.warmup, args.steps)
+    r = loop.run(args.setup_steps, args.warmup, args.steps, full=args.full, dump=args.dump_outputs)
     met = r["metrics"]
     out = {
         "metric": "train rays/sec (800x800 Lego-like, 8192 rays/batch/GPU, full step incl. optimizer)",
@@ -1188,17 +1232,20 @@ def main():
                        "arithmetic, which is held to OUR fp32 restatement of tiny-cuda-nn only (parity unpinned: tiny-cuda-nn is not in the reference tree); "
                        "marching and compositing are pinned to the reference's own kernels",
         "timed_windows": r["timed_windows"], "timed_steps_total": r["timed_steps_total"], "window_ms_per_step_min_max": r["window_ms_per_step_min_max"],
-        "ms_per_step_hip_events": r["ms_per_step_hip_events"], "cold_start": r["cold_start"],
+        "ms_per_step_hip_events": r["ms_per_step_hip_events"],
     }
+    if args.full:
+        out["cold_start"] = r["cold_start"]
     for k in ("exchange", "exchange_impl", "exchange_ms", "exposed_exchange_ms"):
         if k in r:
             out[k] = r[k]
     if "host_ms_per_step" in r:
         out["host_ms_per_step"] = r["host_ms_per_step"]
-    out.update(march_guard_record())
+    if args.full:
+        out.update(march_guard_record())
     keeper.headline(out)
     exchange = loop.exchange
-    if dist is not None and not args.timed_only:
+    if dist is not None and args.full and not args.timed_only:
         # collective legs, every rank, right behind the timed windows and with the exchange still installed: (1) more data-parallel
         # steps, then the evaluation sharded over the ranks; (2) the other exchange modes.  The headline is already with the
         # watchdog: a leg that hangs (a mode that has never run on real links) costs its budget, not the line.
@@ -1219,7 +1266,7 @@ def main():
                     progress("%s failed on rank %d: %s: %s" % (name, rank, type(e).__name__, str(e)[:200]))
     if dist is not None:      # what follows runs on rank 0 only: no collectives from here on
         loop.exchange.uninstall(loop.trainer)
-    if rank == 0 and not args.timed_only:
+    if rank == 0 and args.full and not args.timed_only:
         legs = ["roofline"]
         if not args.no_cpu_baseline and world == 1:
             legs.append("cpu_baseline")

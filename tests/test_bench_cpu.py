@@ -26,7 +26,7 @@ class _FakeLoop:
         self.model, self.data = object(), object()
         self.trainer = types.SimpleNamespace(global_step=545)
 
-    def run(self, setup_steps, warmup, steps, min_timed=200):
+    def run(self, setup_steps, warmup, steps, min_timed=200, full=True, dump=None):
         return dict(rays_per_s=1.0e7, ms_per_step=0.8192, timed_windows=10, timed_steps_total=10 * steps, window_ms_per_step_min_max=[0.8, 0.83],
                     ms_per_step_hip_events=0.81, cold_start={"ms_per_step": 2.0, "window": "steps [5, 25)"},
                     metrics=dict(rm_s=40.0, vr_s=20.0, psnr=25.0, loss=0.01))
@@ -36,7 +36,7 @@ def test_the_line_is_printed_whatever_the_side_legs_do(monkeypatch, capfd, tmp_p
     monkeypatch.setenv("NGP_BENCH_DETAIL", str(tmp_path / "bench_detail.json"))
     b = _load_bench()
     import ngp_pl_amd.bench_support as support
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--secondary"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--secondary", "--full"])
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)
     monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
@@ -112,7 +112,7 @@ class FakeLoop:
     def __init__(self, workload, args, dev, rank, world, dist):
         self.model, self.data = object(), object()
         self.trainer = types.SimpleNamespace(global_step=545)
-    def run(self, setup_steps, warmup, steps, min_timed=200):
+    def run(self, setup_steps, warmup, steps, min_timed=200, full=True, dump=None):
         return dict(rays_per_s=1.0e7, ms_per_step=0.8192, timed_windows=10, timed_steps_total=10 * steps, window_ms_per_step_min_max=[0.8, 0.83],
                     ms_per_step_hip_events=0.81, cold_start=None, metrics=dict(rm_s=40.0, vr_s=20.0, psnr=25.0, loss=0.01))
 b.Loop = FakeLoop
@@ -121,7 +121,7 @@ b.cpu_baseline = lambda model, data: {"value": 100.0, "unit": "rays/s", "cores":
 support.render_fps = lambda model, data, n_frames, **kw: {"fps": 200.0}
 b.api_path_rate = lambda loop: {"rays_per_s": 1.0}
 %s
-sys.argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-secondary", "--deadline", "%g"]
+sys.argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-secondary", "--full", "--deadline", "%g"]
 b.main()
 """ % (ROOT, body, deadline))
     return subprocess.run([sys.executable, str(script)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120,
@@ -164,7 +164,7 @@ support.render_fps = spin
 
 def test_a_hang_before_the_headline_still_prints_one_line_and_fails(tmp_path):
     body = """
-def never(self, setup_steps, warmup, steps, min_timed=200):
+def never(self, setup_steps, warmup, steps, min_timed=200, full=True, dump=None):
     while True:
         pass
 FakeLoop.run = never
@@ -174,6 +174,75 @@ FakeLoop.run = never
     assert r.returncode == 1 and len(lines) == 1, (r.stdout, r.stderr)
     d = json.loads(lines[0])
     assert d["value"] is None and "timeout in setup" in d["error"] and d["steps"] == 20
+
+
+def test_a_plain_run_times_the_steps_and_runs_no_leg(monkeypatch, capfd, tmp_path):
+    """Without --full: one timed window of exactly --steps steps (no cold-start window), the dump directory handed to the loop, the
+    line with the contract fields -- and not one leg, readout or check behind the headline."""
+    monkeypatch.setenv("NGP_BENCH_DETAIL", str(tmp_path / "bench_detail.json"))
+    b = _load_bench()
+    import ngp_pl_amd.bench_support as support
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path / "out")])
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    seen = {}
+
+    class Loop(_FakeLoop):
+        def run(self, setup_steps, warmup, steps, min_timed=200, full=True, dump=None):
+            seen.update(setup_steps=setup_steps, warmup=warmup, steps=steps, full=full, dump=dump)
+            return dict(rays_per_s=1.0e7, ms_per_step=0.8192, timed_windows=1, timed_steps_total=steps, window_ms_per_step_min_max=[0.8192, 0.8192],
+                        ms_per_step_hip_events=0.81, cold_start=None, metrics=dict(rm_s=40.0, vr_s=20.0, psnr=25.0, loss=0.01))
+    monkeypatch.setattr(b, "Loop", Loop)
+
+    def leg(*a, **k):
+        raise AssertionError("a leg ran in a plain run")
+    for name in ("kernel_roofline", "cpu_baseline", "full_run", "api_path_rate", "api_path_plain_rate", "api_path_reference_files_rate",
+                 "secondary_line", "sensitivity", "dp_eval", "march_guard_record"):
+        monkeypatch.setattr(b, name, leg)
+    monkeypatch.setattr(support, "render_fps", leg)
+    saved = os.dup(1)
+    try:
+        b.main()
+    finally:
+        os.dup2(saved, 1); os.close(saved)
+    out, _ = capfd.readouterr()
+    lines = [ln for ln in out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out
+    line = json.loads(lines[0])
+    assert seen == dict(setup_steps=b.SETUP_STEPS, warmup=3, steps=7, full=False, dump=str(tmp_path / "out"))
+    assert line["value"] == 1.0e7 and line["ms_per_step"] == 0.8192 and line["unit"] == "rays/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f16/f32" and line["metric"].startswith("train rays/sec") and line["steps"] == 7 and line["warmup"] == 3
+    assert line["timed_steps_total"] == 7 and line["timed_windows"] == 1
+    assert "roofline" not in line and "cpu_baseline" not in line and "legs_failed" not in line and "error" not in line
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(monkeypatch, tmp_path):
+    """dump_outputs(): float32 / float64 .npy files of the step's record and the parameters; a parameter vector past the byte limit
+    becomes the same seeded sample every time."""
+    import numpy as np
+    b = _load_bench()
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda: None)
+    n = 64
+    last = dict(rgb=torch.rand(n, 3), opacity=torch.rand(n), total=torch.randint(0, 9, (n,)), stats=torch.rand(2), rm_samples=300,
+                n_active=torch.tensor([120], dtype=torch.int32))
+    model = types.SimpleNamespace(rgb_net=types.SimpleNamespace(params=torch.rand(700)), xyz_encoder=types.SimpleNamespace(params=torch.rand(50000)))
+    loop = types.SimpleNamespace(trainer=types.SimpleNamespace(last=last), model=model)
+    b.dump_outputs(loop, str(tmp_path / "all"))
+    got = {f[:-4]: np.load(os.path.join(tmp_path / "all", f)) for f in os.listdir(tmp_path / "all")}
+    assert set(got) == {"rgb", "opacity", "total_samples", "loss_sums", "samples", "rgb_net_params", "xyz_encoder_params"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["rgb"], last["rgb"].numpy()) and np.array_equal(got["total_samples"], last["total"].double().numpy())
+    assert got["samples"].tolist() == [300.0, 120.0] and np.array_equal(got["xyz_encoder_params"], model.xyz_encoder.params.numpy())
+    limit = 100000
+    for d in ("s1", "s2"):
+        b.dump_outputs(loop, str(tmp_path / d), limit=limit)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert "xyz_encoder_params_sample.npy" in files and "xyz_encoder_params.npy" not in files
+    assert sum(os.path.getsize(os.path.join(tmp_path / "s1", f)) for f in files) <= limit
+    s1, s2 = (np.load(os.path.join(tmp_path / d, "xyz_encoder_params_sample.npy")) for d in ("s1", "s2"))
+    assert s1.size > 10000 and np.array_equal(s1, s2) and np.isin(s1, model.xyz_encoder.params.numpy()).all()
 
 
 def test_cpu_baseline_runs_in_a_child_process_and_is_bounded():

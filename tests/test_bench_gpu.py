@@ -26,7 +26,7 @@ def _run_bench(argv, tmp_path, timeout, env=None):
 
 def test_bench_prints_one_json_line_with_roofline_and_cold_start(tmp_path):
     _, line, d = _run_bench(["--gpus", "1", "--steps", "10", "--warmup", "3", "--setup-steps", "48", "--images", "8", "--res", "200",
-                             "--no-cpu-baseline", "--no-render"], tmp_path, 600)
+                             "--no-cpu-baseline", "--no-render", "--full"], tmp_path, 600)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cold_start", "timed_windows", "timed_steps_total", "api_path"):
         assert k in d, k
@@ -54,7 +54,7 @@ def test_driver_command_verbatim(tmp_path):
     and `cpu_baseline`, exit status 0.  (Round 2's driver run of this command was killed at 1800 s with an empty stdout.)"""
     import time
     t = time.perf_counter()
-    r, line, d = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], tmp_path, 300)
+    r, line, d = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], tmp_path, 300)
     wall = time.perf_counter() - t
     assert "error" not in d, (d["error"], r.stderr[-3000:])
     # what the driver parses: value + roofline + cpu_baseline as objects, the three train numbers and both FPS figures as scalars
@@ -101,7 +101,7 @@ def test_bench_under_a_one_rank_rccl_group(exchange, tmp_path):
                NGP_DDP_EXCHANGE=exchange, HSA_ENABLE_IPC_MODE_LEGACY="0", NGP_BENCH_BOTH_MODES="1",      # (the other mode's leg, which only runs at world > 1 otherwise)
                NGP_DP_EVAL_STEPS="100")
     _, line, d = _run_bench(["--gpus", "1", "--steps", "10", "--warmup", "3", "--setup-steps", "48", "--images", "8", "--res", "200",
-                             "--no-cpu-baseline", "--no-render", "--no-api"], tmp_path, 400, env=env)
+                             "--no-cpu-baseline", "--no-render", "--no-api", "--full"], tmp_path, 400, env=env)
     assert "error" not in d, d.get("error")
     # the N-GPU line is the same compact line + what identifies the exchange
     assert line["exchange"] == exchange and line["exchange_impl"] == "native" and line["exchange_ms"] > 0 and line["exposed_exchange_ms"] is not None
@@ -121,3 +121,31 @@ def test_bench_under_a_one_rank_rccl_group(exchange, tmp_path):
     assert ev["rccl_ranks"] == 1 and ev["rccl_rank"] == 0 and ev["rccl_version"] > 20000 and ev["exchange_mode"] == exchange
     assert ev["n_poses"] == 40 and ev["poses_per_rank"] == [40] and len(ev["render_fps_per_gpu"]) == 1 and ev["render_fps_per_gpu"][0] > 1
     assert ev["psnr"] > 10 and ev["render_fps_aggregate"] == ev["render_fps_per_gpu"][0]
+
+
+def test_plain_run_times_exactly_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """The plain command (no --full): ONE timed window of exactly --steps steps, the contract fields, no leg behind the headline; and
+    --dump-outputs writes the last timed step's results as float32/float64 .npy files within 64 MB -- twice the same, since the
+    inputs are seeded and the step is bit-reproducible run to run."""
+    import numpy as np
+    small = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--setup-steps", "24", "--images", "4", "--res", "100"]
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("dump%d" % k)
+        run_dir = tmp_path / ("run%d" % k)
+        run_dir.mkdir()
+        _, line, d = _run_bench(small + ["--dump-outputs", str(out)], run_dir, 300)
+        assert "error" not in d and d["steps"] == 6 and d["timed_windows"] == 1 and d["timed_steps_total"] == 6
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert abs(line["value"] - 8192 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+        assert not {"roofline", "cpu_baseline", "cold_start", "api_path", "full_run", "secondary", "march_guards"} & set(d), sorted(d)
+        files = sorted(os.listdir(out))
+        assert {"rgb.npy", "opacity.npy", "total_samples.npy", "loss_sums.npy", "rgb_net_params.npy", "xyz_encoder_params.npy"} <= set(files)
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 * 2 ** 20
+        arrays = {f: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        assert arrays["rgb.npy"].shape == (8192, 3) and arrays["total_samples.npy"].sum() > 0
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

@@ -1,4 +1,4 @@
-"""CPU, only where /root/reference is mounted: INTEGRATION.md's "Option A" as a test -- the reference's OWN modules
+"""CPU, where the reference is mounted or staged by oracle/build_ref.sh: INTEGRATION.md's "Option A" as a test -- the reference's OWN modules
 (models/rendering.py, models/networks.py, models/custom_functions.py, losses.py) import and construct on top of THIS
 package's bindings after nothing but two module aliases (`vren` -> ngp_pl_amd.vren, `tinycudann` -> ngp_pl_amd.tcnn;
 torch_scatter / kornia, which the hot path does not need from a GPU, get two-line stand-ins).  What it pins: every name,
@@ -7,15 +7,16 @@ compatible signature, and a model built by the reference's own NGP class has exa
 The numerics of the binding are the -m gpu tests' business (no GPU work happens here)."""
 import importlib
 import inspect
-import os
 import sys
 import types
 
 import pytest
 import torch
 
-REFERENCE = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "models")), reason="needs /root/reference")
+from oracle.ref_on_binding import source_dir      # (the reference where mounted, else the copies oracle/build_ref.sh staged)
+
+REFERENCE = source_dir()
+pytestmark = pytest.mark.skipif(REFERENCE is None, reason="the reference's models/*.py are neither mounted nor staged (oracle/build_ref.sh)")
 
 
 @pytest.fixture(scope="module")

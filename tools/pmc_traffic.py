@@ -68,12 +68,12 @@ def main():
     with open(os.path.join(d, "bench_pmc_fetch.json")) as f:
         bench = json.loads([ln for ln in f.read().splitlines() if ln.startswith("{")][-1])
     roof = bench["roofline"]
-    out = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `bench.py --steps 20 --warmup 5 "
+    out = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `bench.py --steps 20 --warmup 5 --full "
                      "--no-render --no-cpu-baseline --no-secondary --no-api`; means over the launches of the last 20 (stage-timed) steps",
            "samples_marched_per_step": roof["samples_marched_per_launch"], "samples_active_per_step": roof["samples_active_per_launch"],
            "stages": {}, "kernel_sum_ms": {}, "issue_bound": {},
            "kernel_sum_ms_how": "sum over the stage's kernels of the average duration in kernel_trace_summary.txt (rocprofv3 --kernel-trace of "
-                                "`bench.py --timed-only`, the 200 timed steps, marching stream running next to them)",
+                                "`bench.py --full --timed-only`, the 200 timed steps, marching stream running next to them)",
            "issue_bound_how": "SQ_ACTIVE_INST_ANY (quad-cycles: x4) / (1024 SIMDs x kernel duration in the same PMC pass x 2400 MHz), the "
                               "stage's longest kernel"}
     for stage, kernels in STAGES.items():
