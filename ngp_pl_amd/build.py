@@ -2,6 +2,8 @@
 
   libngp_hip.so   -- the product: hand-written HIP kernels for gfx950 behind the C ABI of
                      include/ngp_hip.h.  hipcc cross-compiles without a GPU.
+  libngp_mesh.so  -- mesh export (marching cubes over a density volume) behind include/ngp_mesh.h; its sources
+                     live under csrc/mesh/, apart from SOURCES.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -22,6 +24,11 @@ CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=
 # f16, ReLU), and with the accumulator-register form the compiler chose under this register pressure each of those 16-register
 # results cost 16 v_accvgpr_read (208 of the 980 instructions of a backward tile)
 EXTRA = {"mlp.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+MESH_LIB = os.path.join(CSRC, "libngp_mesh.so")
+MESH_SOURCES = [os.path.join("mesh", "mesh.hip")]
+MESH_HEADERS = [os.path.join("mesh", "mc_tables.h"), os.path.join("..", "..", "include", "ngp_mesh.h")]
+# positions and normals are the plain f32 expressions of include/ngp_mesh.h (no fused multiply-add), as tests/mc_reference.py has them
+MESH_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -38,24 +45,31 @@ def _run(cmd):
     return r.stdout
 
 
-def build(force=False, verbose=False):
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS]
+def _plan(sources, headers, extra, force):
+    hdrs = [os.path.join(CSRC, h) for h in headers]
     objs, jobs = [], []
-    for src in SOURCES:
+    for src in sources:
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, src.replace(".hip", ".o"))
         objs.append(o)
         if force or _stale(o, [s, os.path.abspath(__file__)] + hdrs):
-            jobs.append([HIPCC] + CFLAGS + EXTRA.get(src, []) + ["-c", s, "-o", o])
-    if jobs:
+            jobs.append([HIPCC] + CFLAGS + extra(src) + ["-c", s, "-o", o])
+    return objs, jobs
+
+
+def build(force=False, verbose=False):
+    objs, jobs = _plan(SOURCES, HEADERS, lambda src: EXTRA.get(src, []), force)
+    mesh_objs, mesh_jobs = _plan(MESH_SOURCES, MESH_HEADERS, lambda src: MESH_CFLAGS, force)
+    if jobs or mesh_jobs:
         if verbose:
-            print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(jobs), ARCH))
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex:
-            list(ex.map(_run, jobs))
-    if force or jobs or _stale(LIB, objs):
-        _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + objs + ["-o", LIB])
-        if verbose:
-            print("[ngp_pl_amd.build] linked", LIB)
+            print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(jobs) + len(mesh_jobs), ARCH))
+        with ThreadPoolExecutor(max_workers=min(len(jobs) + len(mesh_jobs), os.cpu_count() or 1)) as ex:
+            list(ex.map(_run, jobs + mesh_jobs))
+    for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs)):
+        if force or changed or _stale(lib, o):
+            _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
+            if verbose:
+                print("[ngp_pl_amd.build] linked", lib)
     return LIB
 
 

@@ -1,0 +1,219 @@
+"""Mesh export of a trained field: density on a lattice, marching cubes on the GPU (libngp_mesh.so), a binary PLY writer and a CLI.
+
+    vol = density_volume(model, resolution=512)                    # (nz, ny, nx) f32 on the model's device
+    m = marching_cubes(vol, threshold=20.0, bounds=(lo3, hi3))     # Mesh(vertices (V,3) f32, faces (F,3) i32, normals (V,3) f32)
+    m = extract_mesh(model, resolution=512, threshold=20.0, colors=True)
+    save_ply("mesh.ply", m)
+
+    python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] --out mesh.ply
+
+Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
+[k, j, i]; vertices come back in world coordinates.  The reference's notebook (test.ipynb) instead samples
+np.meshgrid(x, y, z) with the default 'xy' indexing (its axis 0 is y) and scales index-space vertices by 1/N: a notebook vertex
+u = (u0, u1, u2) is the world point lo + N * (u1, u0, u2) * (hi - lo) / (N - 1) of this API.  The default threshold 20 is the notebook's
+sigma_threshold.  The occupancy grid is not used: every lattice point is evaluated.  There is no CPU path.
+"""
+import argparse
+import ctypes as C
+import dataclasses
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib, _mesh_lib
+from ._mesh_lib import bounds6, device_guard, ptr, stream
+
+INT32_MAX = 2 ** 31 - 1
+
+
+@dataclasses.dataclass
+class Mesh:
+    vertices: object            # (V, 3) f32, world coordinates
+    faces: object               # (F, 3) i32, counter-clockwise seen from outside
+    normals: object = None      # (V, 3) f32, unit, outward (density falls outward); 0 where the gradient vanishes
+    colors: object = None       # (V, 3) f32 RGB in [0, 1], or None
+
+
+def _resolution(resolution):
+    r = (resolution,) * 3 if isinstance(resolution, int) else tuple(int(v) for v in resolution)
+    if len(r) != 3 or min(r) < 2:
+        raise ValueError("resolution must be an int or (nx, ny, nz), each >= 2: %r" % (resolution,))
+    return r
+
+
+def _box(model):
+    return model.xyz_min.view(-1).tolist(), model.xyz_max.view(-1).tolist()
+
+
+def _bounds(model, bounds):
+    blo, bhi = _box(model)
+    if bounds is None:
+        return blo, bhi
+    lo, hi = [float(v) for v in bounds[0]], [float(v) for v in bounds[1]]
+    if len(lo) != 3 or len(hi) != 3 or any(not (a < b) for a, b in zip(lo, hi)):
+        raise ValueError("bounds must be (lo3, hi3) with lo < hi: %r" % (bounds,))
+    if any(a < m for a, m in zip(lo, blo)) or any(b > m for b, m in zip(hi, bhi)):
+        raise ValueError("bounds %r leave the model's box (%r, %r)" % (bounds, blo, bhi))
+    return lo, hi
+
+
+def _require_cuda(t, what):
+    if not t.is_cuda:
+        raise RuntimeError("%s must be a CUDA (HIP) tensor: mesh export has no CPU path" % what)
+
+
+@torch.no_grad()
+def density_volume(model, resolution=512, bounds=None, chunk=1 << 22):
+    """model.density at every lattice point of `bounds` (default: the model's box): (nz, ny, nx) f32 on the model's device.  Each
+    chunk of lattice points goes through ngp_hashgrid_fwd + ngp_density_fwd, the sigmas straight into the volume."""
+    nx, ny, nz = _resolution(resolution)
+    lo, hi = _bounds(model, bounds)
+    _require_cuda(model.xyz_min, "the model")
+    dev = model.xyz_min.device
+    vol = torch.empty(nz, ny, nx, dtype=torch.float32, device=dev)
+    n = vol.numel()
+    chunk = int(min(chunk, n, INT32_MAX))
+    enc = model.xyz_encoder
+    eh = enc._half.get(enc.params)
+    xyz = torch.empty(chunk, 3, dtype=torch.float32, device=dev)
+    feats = torch.empty(16, chunk, 2, dtype=torch.float16, device=dev)
+    b6 = bounds6(lo, hi)
+    with device_guard(dev):
+        s = stream()
+        for begin in range(0, n, chunk):
+            cnt = min(chunk, n - begin)
+            _mesh_lib.call("ngp_mesh_lattice_points", nx, ny, nz, b6, begin, cnt, ptr(xyz), s)
+            _lib.call("ngp_hashgrid_fwd", ptr(xyz), ptr(model.xyz_min), ptr(model.xyz_max), ptr(eh[enc.n_mlp:]), C.byref(enc.meta), cnt,
+                      ptr(feats), s)
+            _lib.call("ngp_density_fwd", ptr(feats), ptr(eh), cnt, vol.data_ptr() + 4 * begin, None, s)
+    return vol
+
+
+def lattice_points(resolution, bounds, device="cuda", begin=0, count=None):
+    """World coordinates (count, 3) of lattice points begin .. begin+count-1, as density_volume samples them."""
+    nx, ny, nz = _resolution(resolution)
+    n = nx * ny * nz
+    count = n - begin if count is None else count
+    xyz = torch.empty(count, 3, dtype=torch.float32, device=device)
+    _require_cuda(xyz, "device")
+    with device_guard(xyz.device):
+        _mesh_lib.call("ngp_mesh_lattice_points", nx, ny, nz, bounds6(*bounds), begin, count, ptr(xyz), stream())
+    return xyz
+
+
+def marching_cubes(vol, threshold=20.0, bounds=None):
+    """Indexed triangle mesh of {vol > threshold} (include/ngp_mesh.h has the exact rules).  `bounds` = (lo3, hi3) of the lattice
+    in world units; None puts lattice point (i, j, k) at (i, j, k).  One host sync (the totals, to size the outputs)."""
+    if not isinstance(vol, torch.Tensor) or vol.dim() != 3 or vol.dtype != torch.float32:
+        raise ValueError("vol must be a (nz, ny, nx) float32 tensor")
+    _require_cuda(vol, "vol")
+    vol = vol.contiguous()
+    nz, ny, nx = vol.shape
+    if bounds is None:
+        bounds = ((0.0, 0.0, 0.0), (nx - 1.0, ny - 1.0, nz - 1.0))
+    b6 = bounds6(*bounds)
+    h = _mesh_lib.lib()
+    ws_bytes = h.ngp_mesh_workspace_bytes(nx, ny, nz)
+    if ws_bytes == 0:
+        raise ValueError("volume shape %r out of range (each axis 2..65535)" % (tuple(vol.shape),))
+    dev = vol.device
+    with device_guard(dev):
+        s = stream()
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        _mesh_lib.call("ngp_mesh_count", ptr(vol), nx, ny, nz, float(threshold), ptr(ws), ws_bytes, ptr(totals), s)
+        n_v, n_f = totals.tolist()
+        if n_v > INT32_MAX or n_f > INT32_MAX:
+            raise _lib.NgpError("ngp_mesh_count: %d vertices, %d faces: NGP_ERANGE (int32 indices)" % (n_v, n_f))
+        verts = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+        normals = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
+        _mesh_lib.call("ngp_mesh_emit", ptr(vol), nx, ny, nz, float(threshold), b6, ptr(ws), ws_bytes, n_v, n_f, ptr(verts), ptr(normals),
+                       ptr(faces), s)
+    return Mesh(verts, faces, normals)
+
+
+@torch.no_grad()
+def vertex_colors(model, vertices, normals, chunk=1 << 20):
+    """RGB of the field at each vertex, seen along -normal (direction (0, 0, 1) where the normal is zero), through the model's
+    no-grad forward."""
+    d = -normals
+    d[(normals == 0).all(1)] = torch.tensor([0.0, 0.0, 1.0], device=d.device)
+    out = torch.empty_like(vertices)
+    for b in range(0, vertices.shape[0], chunk):
+        _, rgb = model(vertices[b:b + chunk].contiguous(), d[b:b + chunk].contiguous())
+        out[b:b + chunk] = rgb.float()
+    return out
+
+
+def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False):
+    """density_volume + marching_cubes in the model's world coordinates; colors=True adds vertex_colors."""
+    lo, hi = _bounds(model, bounds)
+    vol = density_volume(model, resolution, (lo, hi))
+    m = marching_cubes(vol, threshold, (lo, hi))
+    del vol
+    if colors:
+        m.colors = vertex_colors(model, m.vertices, m.normals)
+    return m
+
+
+def _np(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def save_ply(path, m):
+    """Binary little-endian PLY: x y z (float), nx ny nz (float) when normals exist, red green blue (uchar) when colors exist,
+    faces as `list uchar int vertex_indices`."""
+    v = _np(m.vertices).astype("<f4").reshape(-1, 3)
+    f = _np(m.faces).astype("<i4").reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if m.normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if m.colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    rec = np.empty(len(v), dtype=fields)
+    rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if m.normals is not None:
+        n = _np(m.normals).astype("<f4").reshape(-1, 3)
+        rec["nx"], rec["ny"], rec["nz"] = n[:, 0], n[:, 1], n[:, 2]
+    if m.colors is not None:
+        c = np.clip(np.round(_np(m.colors).astype(np.float64) * 255.0), 0, 255).astype(np.uint8).reshape(-1, 3)
+        rec["red"], rec["green"], rec["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    frec = np.empty(len(f), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    frec["n"] = 3
+    frec["v"] = f
+    head = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v)]
+    head += ["property %s %s" % ("float" if t == "<f4" else "uchar", name) for name, t in fields]
+    head += ["element face %d" % len(f), "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(head) + "\n").encode("ascii"))
+        out.write(rec.tobytes())
+        out.write(frec.tobytes())
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m ngp_pl_amd.mesh", description="Extract a mesh from a trained checkpoint (binary PLY).")
+    ap.add_argument("--ckpt", required=True, help="checkpoint (Lightning .ckpt or a slim state dict)")
+    ap.add_argument("--scale", type=float, default=0.5, help="scene scale the model was trained with")
+    ap.add_argument("--level-table", default="float32", choices=("float32", "exact"), help="hash-grid level table of the checkpoint")
+    ap.add_argument("--resolution", type=int, nargs="+", default=[512], help="N, or nx ny nz")
+    ap.add_argument("--threshold", type=float, default=20.0, help="density iso-level (the notebook's sigma_threshold)")
+    ap.add_argument("--colors", action="store_true", help="add vertex colours (the field seen along -normal)")
+    ap.add_argument("--out", required=True, help="output .ply")
+    a = ap.parse_args(argv)
+    if len(a.resolution) not in (1, 3):
+        ap.error("--resolution takes N or nx ny nz")
+    from .networks import NGP
+    from .utils import load_ckpt
+    model = NGP(scale=a.scale, level_table=a.level_table).cuda()
+    load_ckpt(model, a.ckpt, prefixes_to_ignore=("density_grid", "grid_coords"))
+    res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
+    m = extract_mesh(model, res, a.threshold, colors=a.colors)
+    save_ply(a.out, m)
+    print("%s: %d vertices, %d faces" % (a.out, m.vertices.shape[0], m.faces.shape[0]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
