@@ -17,17 +17,10 @@ typedef _Float16 h1;
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// Dynamic loss scale on the device (torch.cuda.amp.GradScaler's rule, which Lightning's precision=16 puts on top of tiny-cuda-nn's
-// fixed 128 in the reference, train.py:274): state = {f32 scale[2], i32 growth_tracker[2]}.  The launches of a step read slot
-// `slot` (the field backward multiplies its seeds by scale[slot], this kernel divides the gradients by it -- powers of two: exact);
-// the first MLP workgroup writes slot ^ 1: scale * backoff and tracker 0 when the step's flag is raised, else tracker + 1, and
-// scale * growth every `interval` clean steps.  Readers and the writer never share a word inside a launch.
-struct LossScaler { float* state; int slot; float growth, backoff; int interval; float lo, hi; };
-
 struct AdamHyper { float lr, beta1, beta2, eps, wd, bc1, bc2, inv_scale; const int32_t* found_inf; int zero_grad;
                    const int32_t* found_inf_dense;        // skip flag of the dense (grid) block: found_inf unless a caller gives it its own
                    int32_t* step_state; int slot;         // device-side counts of APPLIED steps (below), or NULL: bc1 / bc2 as given
-                   LossScaler scaler; };                  // state == NULL: none
+                   LossScaler scaler; };
 
 // Bias correction under a skip flag.  apex / GradScaler leave the optimizer's step count unchanged when a step is skipped; the host
 // cannot know whether the device-side flag was raised without a sync, so the count of APPLIED steps lives next to the flag:
@@ -68,22 +61,45 @@ __device__ __forceinline__ h1 sat_f16(float v) { return (h1)fminf(fmaxf(v, -6550
 // (ngp_grid_partials, include/ngp_hip.h): device-side copy of the record.
 struct GridPartials { long long value_end; uint32_t offset[8]; int k_split[8]; long long part_off[8]; const float2* partial; int n_levels; };
 
+// This rank's PIECES of an exchanged table (csrc/comm.hip, stepper tail): the table is exchanged in n_chunks chunks of world x piece
+// values; the rank updates values [c * chunk + rank * piece, + piece) of every chunk c from the reduce-scatter's output, which holds
+// its pieces back to back.  piece is a multiple of 8 and n_grid of 16, so neither a piece boundary nor the end of the table falls
+// inside a group of 4.
+struct AdamPieces { long long piece, chunk, rank_off; };
+
+// Where the dense block's gradient comes from.  Chosen at compile time: the merge pass streams near the HBM floor, and a switch inside
+// the loop would cost it.
+//   F16        the f16 gradient, clamped to +-65504; zeroed behind the read if hp.zero_grad (also when the step is skipped)
+//   F32        an f32 gradient (ngp_adam_step), not clamped; zeroed like F16
+//   F16_MERGE  values below gp->value_end formed here from the K partial tables, summed in part order in f32 and rounded to f16
+//              exactly as merge_kernel (hashgrid_bwd_binned.hip) does -- bit-identical to merge + F16; the rest as F16; never zeroed
+//   PIECES     gradient value i of the rank's pieces (pc) updates parameter c * chunk + rank_off + (i - c * piece), padding behind the
+//              n-parameter table skipped; not clamped, not zeroed, param_h always written; nothing is loaded under the skip flag
+enum class Src { F16, F32, F16_MERGE, PIECES };
+
 // Dense (streaming) update of n parameters by workgroups `block` of `n_blocks`, 4 parameters per thread and trip.
-// MERGE: gradient values below gp.value_end are formed here from the K partial tables -- summed in part order in f32 and rounded to
-// f16 exactly as merge_kernel (hashgrid_bwd_binned.hip) does, so the update is bit-identical to merge + this kernel without MERGE.
-template <bool GRAD_F32, bool MERGE = false>
+template <Src S>
 __device__ __forceinline__ void adam_dense(float* __restrict__ param, h1* __restrict__ param_h, void* __restrict__ grad,
                                            float* __restrict__ m, float* __restrict__ v, long long n4, long long n,
-                                           const AdamHyper& hp, int block, int n_blocks, const GridPartials* gp = nullptr) {
+                                           const AdamHyper& hp, int block, int n_blocks, const GridPartials* gp = nullptr,
+                                           const AdamPieces* pc = nullptr) {
+    constexpr bool ZERO = S != Src::PIECES;      // (F16_MERGE is handed zero_grad = 0; the run-time test keeps its code as measured)
     const AdamCoef coef = {hp.lr, hp.beta1, hp.beta2, hp.eps, hp.wd, hp.bc1, hp.bc2, hp.inv_scale};
     const bool skip = hp.found_inf_dense != nullptr && *hp.found_inf_dense != 0;
+    if (S == Src::PIECES && skip) return;
     const long long stride = (long long)n_blocks * blockDim.x;
     for (long long q = (long long)block * blockDim.x + threadIdx.x; q < n4; q += stride) {
-        const long long base = q * 4;
+        const long long i = q * 4;                                        // gradient index
+        long long base = i;                                               // parameter index
+        if (S == Src::PIECES) {
+            const long long c = i / pc->piece;
+            base = c * pc->chunk + pc->rank_off + (i - c * pc->piece);
+            if (base >= n) continue;                                      // padding behind the table
+        }
         float g[4];
-        const int cnt = (int)((n - base) < 4 ? (n - base) : 4);
+        const int cnt = S == Src::PIECES ? 4 : (int)((n - base) < 4 ? (n - base) : 4);
         if (cnt == 4) {
-            if (MERGE && base < gp->value_end) {
+            if (S == Src::F16_MERGE && base < gp->value_end) {
                 // two entries of one level (levels are multiples of 8 entries long): sum their K partials
                 const uint32_t e0 = (uint32_t)(base >> 1);
                 int l = 0;
@@ -96,18 +112,18 @@ __device__ __forceinline__ void adam_dense(float* __restrict__ param, h1* __rest
                     a0 += t.x; b0 += t.y; a1 += t.z; b1 += t.w;
                 }
                 g[0] = (float)sat_f16(a0); g[1] = (float)sat_f16(b0); g[2] = (float)sat_f16(a1); g[3] = (float)sat_f16(b1);     // (as merge_kernel)
-            } else if (GRAD_F32) {
+            } else if (S == Src::F32) {
                 float4* gp4 = reinterpret_cast<float4*>(reinterpret_cast<float*>(grad) + base);
                 const float4 t = *gp4; g[0] = t.x; g[1] = t.y; g[2] = t.z; g[3] = t.w;
                 if (hp.zero_grad) *gp4 = make_float4(0.f, 0.f, 0.f, 0.f);
             } else {
-                half4_t* gp4 = reinterpret_cast<half4_t*>(reinterpret_cast<h1*>(grad) + base);
+                half4_t* gp4 = reinterpret_cast<half4_t*>(reinterpret_cast<h1*>(grad) + i);
                 const half4_t t = *gp4;
                 // (an f16 gradient is finite unless a path that sums in f16 overflowed -- the one-pass fallback of oversized batches, a
                 // reduce-scatter of the ranks' tables: +-65504 instead of inf / NaN keeps the moments finite; free on this stream)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) g[k] = fminf(fmaxf((float)t[k], -65504.0f), 65504.0f);
-                if (hp.zero_grad) { const half4_t z = {0, 0, 0, 0}; *gp4 = z; }
+                for (int k = 0; k < 4; ++k) g[k] = S == Src::PIECES ? (float)t[k] : fminf(fmaxf((float)t[k], -65504.0f), 65504.0f);
+                if (ZERO && hp.zero_grad) { const half4_t z = {0, 0, 0, 0}; *gp4 = z; }
             }
             if (skip) continue;
             float4 p = *reinterpret_cast<float4*>(param + base);
@@ -123,18 +139,18 @@ __device__ __forceinline__ void adam_dense(float* __restrict__ param, h1* __rest
             *reinterpret_cast<float4*>(param + base) = p;
             *reinterpret_cast<float4*>(m + base) = mm;
             *reinterpret_cast<float4*>(v + base) = vv;
-            if (param_h) *reinterpret_cast<half4_t*>(param_h + base) = ph;
-        } else {
+            if (S == Src::PIECES || param_h) *reinterpret_cast<half4_t*>(param_h + base) = ph;
+        } else if (S != Src::PIECES) {
             for (int k = 0; k < cnt; ++k) {
-                const long long i = base + k;
+                const long long j = base + k;
                 float gk;
-                if (GRAD_F32) { float* gp = reinterpret_cast<float*>(grad) + i; gk = *gp; if (hp.zero_grad) *gp = 0.f; }
-                else { h1* gp = reinterpret_cast<h1*>(grad) + i; gk = fminf(fmaxf((float)*gp, -65504.0f), 65504.0f); if (hp.zero_grad) *gp = (h1)0; }
+                if (S == Src::F32) { float* gq = reinterpret_cast<float*>(grad) + j; gk = *gq; if (hp.zero_grad) *gq = 0.f; }
+                else { h1* gq = reinterpret_cast<h1*>(grad) + j; gk = fminf(fmaxf((float)*gq, -65504.0f), 65504.0f); if (ZERO && hp.zero_grad) *gq = (h1)0; }
                 if (skip) continue;
-                float pk = param[i], mk = m[i], vk = v[i];
+                float pk = param[j], mk = m[j], vk = v[j];
                 adam_one(pk, mk, vk, gk, coef);
-                m[i] = mk; v[i] = vk; param[i] = pk;
-                if (param_h) param_h[i] = (h1)pk;
+                m[j] = mk; v[j] = vk; param[j] = pk;
+                if (param_h) param_h[j] = (h1)pk;
             }
         }
     }
@@ -144,38 +160,13 @@ template <bool GRAD_F32>
 __global__ void __launch_bounds__(256)
 adam_kernel(float* __restrict__ param, h1* __restrict__ param_h, void* __restrict__ grad,
             float* __restrict__ m, float* __restrict__ v, long long n4, long long n, AdamHyper hp) {
-    adam_dense<GRAD_F32>(param, param_h, grad, m, v, n4, n, hp, blockIdx.x, gridDim.x);
-}
-
-// out[i] = sum_p partials[p][i].  32 columns x 8 row lanes per workgroup, 4 independent loads in
-// flight per thread (a thread per column walking all rows serially measured 62 us for 256 x 10240
-// on MI355X, 64 columns x 4 row lanes 21 us).
-__global__ void __launch_bounds__(256)
-reduce_partials_kernel(const float* __restrict__ partials, int n_partials, int n, float* __restrict__ out) {
-    __shared__ float s_acc[8][32];
-    const int c = threadIdx.x & 31, lane_row = threadIdx.x >> 5;
-    const int col = blockIdx.x * 32 + c;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (col < n) {
-        int p = lane_row;
-        for (; p + 24 < n_partials; p += 32) {
-            a0 += partials[(size_t)p * n + col]; a1 += partials[(size_t)(p + 8) * n + col];
-            a2 += partials[(size_t)(p + 16) * n + col]; a3 += partials[(size_t)(p + 24) * n + col];
-        }
-        for (; p < n_partials; p += 8) a0 += partials[(size_t)p * n + col];
-    }
-    s_acc[lane_row][c] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (lane_row == 0 && col < n) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) t += s_acc[r][c];
-        out[col] = t;
-    }
+    adam_dense<GRAD_F32 ? Src::F32 : Src::F16>(param, param_h, grad, m, v, n4, n, hp, blockIdx.x, gridDim.x);
 }
 
 // Adam for the small MLP blocks straight from the per-workgroup partial sums: one thread per
-// parameter sums its column of `partials` (n_partials x n) and applies the update.
+// parameter sums its column of `partials` (n_partials x n) and applies the update.  Its bits are the contract: the column sum (2
+// accumulators, not reduce_partials2_kernel's 4) and the update written out here rather than through adam_one, whose expression
+// contracts into different FMAs in these kernels.
 __device__ __forceinline__ void adam_from_partials(float* __restrict__ param, h1* __restrict__ param_h, const float* __restrict__ partials,
                                                    int n_partials, float* __restrict__ m, float* __restrict__ v, int n,
                                                    const AdamHyper& hp, int block, float (*s_acc)[32]) {
@@ -212,72 +203,18 @@ adam_partials_kernel(float* __restrict__ param, h1* __restrict__ param_h, const 
 // The whole field in ONE launch: the two MLP blocks (from their partial sums; latency-bound, a few hundred
 // workgroups) are dispatched first and run underneath the HBM-bound stream over the grid parameters.
 struct AdamMlp { float* param; h1* param_h; const float* partials; float* m; float* v; int n; int blocks; };
+template <Src S>
 __global__ void __launch_bounds__(256)
-adam_field_kernel(float* __restrict__ param, h1* __restrict__ param_h, void* __restrict__ grad16, float* __restrict__ m,
-                  float* __restrict__ v, long long n4, long long n, AdamMlp a, AdamMlp b, int n_partials, AdamHyper hp) {
+adam_field_kernel(float* __restrict__ param, h1* __restrict__ param_h, void* __restrict__ grad, float* __restrict__ m,
+                  float* __restrict__ v, long long n4, long long n, AdamMlp a, AdamMlp b, int n_partials, AdamHyper hp,
+                  GridPartials gp, AdamPieces pc) {
     __shared__ float s_acc[8][32];
     const int blk = blockIdx.x;
     const bool dense = blk >= a.blocks + b.blocks;
     adam_bias_from_state(hp, dense, blk == 0 || blk == a.blocks + b.blocks);
     if (blk < a.blocks) adam_from_partials(a.param, a.param_h, a.partials, n_partials, a.m, a.v, a.n, hp, blk, s_acc);
     else if (!dense) adam_from_partials(b.param, b.param_h, b.partials, n_partials, b.m, b.v, b.n, hp, blk - a.blocks, s_acc);
-    else adam_dense<false>(param, param_h, grad16, m, v, n4, n, hp, blk - a.blocks - b.blocks, (int)gridDim.x - a.blocks - b.blocks);
-}
-
-// The same launch for a data-parallel rank that owns one PIECE of every chunk of the table (csrc/comm.hip, stepper tail): the
-// table is exchanged in n_chunks chunks of world x piece values; this rank updates values [c * chunk + rank * piece, + piece) of
-// every chunk c from the reduce-scatter's output, which holds the rank's pieces back to back.  piece is a multiple of 8 and
-// n_grid of 16, so neither a piece boundary nor the end of the table falls inside a group of 4.
-struct AdamPieces { long long piece, chunk, rank_off, n_grid; int n_chunks; };
-__device__ __forceinline__ void adam_dense_pieces(float* __restrict__ param, h1* __restrict__ param_h, const h1* __restrict__ grad,
-                                                  float* __restrict__ m, float* __restrict__ v, const AdamPieces pc,
-                                                  const AdamHyper& hp, int block, int n_blocks) {
-    const AdamCoef coef = {hp.lr, hp.beta1, hp.beta2, hp.eps, hp.wd, hp.bc1, hp.bc2, hp.inv_scale};
-    if (hp.found_inf_dense != nullptr && *hp.found_inf_dense != 0) return;
-    const long long n4 = (long long)pc.n_chunks * pc.piece / 4, stride = (long long)n_blocks * blockDim.x;
-    for (long long q = (long long)block * blockDim.x + threadIdx.x; q < n4; q += stride) {
-        const long long i = q * 4, c = i / pc.piece, base = c * pc.chunk + pc.rank_off + (i - c * pc.piece);
-        if (base >= pc.n_grid) continue;                                   // padding behind the table
-        const half4_t t = *reinterpret_cast<const half4_t*>(grad + i);
-        float4 p = *reinterpret_cast<float4*>(param + base);
-        float4 mm = *reinterpret_cast<float4*>(m + base);
-        float4 vv = *reinterpret_cast<float4*>(v + base);
-        float* pp = &p.x; float* mp = &mm.x; float* vp = &vv.x;
-        half4_t ph;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            adam_one(pp[k], mp[k], vp[k], (float)t[k], coef);
-            ph[k] = (h1)pp[k];
-        }
-        *reinterpret_cast<float4*>(param + base) = p;
-        *reinterpret_cast<float4*>(m + base) = mm;
-        *reinterpret_cast<float4*>(v + base) = vv;
-        *reinterpret_cast<half4_t*>(param_h + base) = ph;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-adam_field_pieces_kernel(float* __restrict__ param, h1* __restrict__ param_h, const h1* __restrict__ shard16, float* __restrict__ m,
-                         float* __restrict__ v, AdamPieces pc, AdamMlp a, AdamMlp b, int n_partials, AdamHyper hp) {
-    __shared__ float s_acc[8][32];
-    const int blk = blockIdx.x;
-    const bool dense = blk >= a.blocks + b.blocks;
-    adam_bias_from_state(hp, dense, blk == 0 || blk == a.blocks + b.blocks);
-    if (blk < a.blocks) adam_from_partials(a.param, a.param_h, a.partials, n_partials, a.m, a.v, a.n, hp, blk, s_acc);
-    else if (!dense) adam_from_partials(b.param, b.param_h, b.partials, n_partials, b.m, b.v, b.n, hp, blk - a.blocks, s_acc);
-    else adam_dense_pieces(param, param_h, shard16, m, v, pc, hp, blk - a.blocks - b.blocks, (int)gridDim.x - a.blocks - b.blocks);
-}
-
-__global__ void __launch_bounds__(256)
-adam_field_merge_kernel(float* __restrict__ param, h1* __restrict__ param_h, void* __restrict__ grad16, float* __restrict__ m,
-                        float* __restrict__ v, long long n4, long long n, AdamMlp a, AdamMlp b, int n_partials, AdamHyper hp, GridPartials gp) {
-    __shared__ float s_acc[8][32];
-    const int blk = blockIdx.x;
-    const bool dense = blk >= a.blocks + b.blocks;
-    adam_bias_from_state(hp, dense, blk == 0 || blk == a.blocks + b.blocks);
-    if (blk < a.blocks) adam_from_partials(a.param, a.param_h, a.partials, n_partials, a.m, a.v, a.n, hp, blk, s_acc);
-    else if (!dense) adam_from_partials(b.param, b.param_h, b.partials, n_partials, b.m, b.v, b.n, hp, blk - a.blocks, s_acc);
-    else adam_dense<false, true>(param, param_h, grad16, m, v, n4, n, hp, blk - a.blocks - b.blocks, (int)gridDim.x - a.blocks - b.blocks, &gp);
+    else adam_dense<S>(param, param_h, grad, m, v, n4, n, hp, blk - a.blocks - b.blocks, (int)gridDim.x - a.blocks - b.blocks, &gp, &pc);
 }
 
 __global__ void __launch_bounds__(256)
@@ -440,34 +377,14 @@ get_rays_kernel(const float* __restrict__ directions, const float* __restrict__ 
     }
 }
 
-// GradScaler's inf check (torch.amp.GradScaler.unscale_ -> _amp_foreach_non_finite_check_and_unscale_) on a native
-// gradient buffer: flag[0] |= 1 if any element is inf/NaN.  16 bytes per lane and trip; f16 exponent all-ones test on the raw bits.
-__global__ void __launch_bounds__(256)
-found_inf_kernel(const u32x4* __restrict__ g, long long n16, const unsigned short* __restrict__ tail, int n_tail, int is_half,
-                 int32_t* __restrict__ flag) {
-    bool bad = false;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < n16; q += stride) {
-        const u32x4 w = __builtin_nontemporal_load(g + q);
-        const uint32_t x[4] = {w[0], w[1], w[2], w[3]};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (is_half) bad |= ((x[k] & 0x7c00u) == 0x7c00u) | ((x[k] & 0x7c000000u) == 0x7c000000u);
-            else bad |= (x[k] & 0x7f800000u) == 0x7f800000u;
-        }
-    }
-    if (blockIdx.x == 0 && (int)threadIdx.x < n_tail) {          // the < 16 trailing bytes, as 16-bit words
-        if (is_half) bad |= (tail[threadIdx.x] & 0x7c00u) == 0x7c00u;
-        else if (threadIdx.x & 1) bad |= (tail[threadIdx.x] & 0x7f80u) == 0x7f80u;
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
-}
-
-// The same check over TWO buffers in one launch (the reduced grid gradient and the reduced MLP sums), with the flag of the
-// NEXT step cleared on the side: callers alternate between two flags, so no memset launch is needed in steady state.
+// GradScaler's inf check (torch.amp.GradScaler.unscale_ -> _amp_foreach_non_finite_check_and_unscale_) on native gradient
+// buffers: flag[0] |= 1 if any element of a or b is inf/NaN.  16 bytes per lane and trip; f16 exponent all-ones test on the raw bits;
+// `tail`: the < 16 trailing bytes of a, as 16-bit words.  Two buffers in one launch (the reduced grid gradient and the reduced MLP
+// sums), with the flag of the NEXT step cleared on the side: callers alternate between two flags, so no memset launch is needed in
+// steady state.
 __global__ void __launch_bounds__(256)
 found_inf2_kernel(const u32x4* __restrict__ a, long long a16, int a_half, const u32x4* __restrict__ b, long long b16, int b_half,
-                  int32_t* __restrict__ flag, int32_t* __restrict__ flag_clear) {
+                  const unsigned short* __restrict__ tail, int n_tail, int32_t* __restrict__ flag, int32_t* __restrict__ flag_clear) {
     bool bad = false;
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < a16 + b16; q += stride) {
@@ -481,12 +398,18 @@ found_inf2_kernel(const u32x4* __restrict__ a, long long a16, int a_half, const 
             else bad |= (x[k] & 0x7f800000u) == 0x7f800000u;
         }
     }
+    if (blockIdx.x == 0 && (int)threadIdx.x < n_tail) {
+        if (a_half) bad |= (tail[threadIdx.x] & 0x7c00u) == 0x7c00u;
+        else if (threadIdx.x & 1) bad |= (tail[threadIdx.x] & 0x7f80u) == 0x7f80u;
+    }
     if (flag_clear && blockIdx.x == 0 && threadIdx.x == 0) *flag_clear = 0;
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
 // out[0:n_a] = column sums of partials_a (n_partials, n_a), out[n_a:n_a+n_b] = column sums of partials_b (n_partials, n_b): both MLP
-// blocks' per-workgroup partial sums in one launch (reduce_partials_kernel's scheme).
+// blocks' per-workgroup partial sums in one launch (n_b = 0: one block).  32 columns x 8 row lanes per workgroup, 4 independent loads
+// in flight per thread (a thread per column walking all rows serially measured 62 us for 256 x 10240 on MI355X, 64 columns x 4 row
+// lanes 21 us).
 __global__ void __launch_bounds__(256)
 reduce_partials2_kernel(const float* __restrict__ pa, int n_a, const float* __restrict__ pb, int n_b, int n_partials, float* __restrict__ out) {
     __shared__ float s_acc[8][32];
@@ -515,19 +438,27 @@ reduce_partials2_kernel(const float* __restrict__ pa, int n_a, const float* __re
     }
 }
 
-// (csrc/ngp_internal.h: ngp_adam_use_loss_scaler) the scaler of the NEXT optimizer launch this thread enqueues; consumed by it
+// (csrc/ngp_internal.h: ngp_adam_use_loss_scaler) the scaler of the NEXT optimizer launch this thread enqueues through the ABI
 thread_local LossScaler t_next_scaler = {nullptr, 0, 2.0f, 0.5f, 2000, 1.0f, 1.0f};
 
-AdamHyper adam_hyper(float lr, float beta1, float beta2, float eps, float wd, int step, float grad_scale, const int32_t* found_inf) {
-    AdamHyper hp;
-    hp.scaler = t_next_scaler;
+LossScaler take_scaler() {
+    const LossScaler q = t_next_scaler;
     t_next_scaler.state = nullptr;
+    return q;
+}
+
+AdamHyper adam_hyper(float lr, float beta1, float beta2, float eps, float wd, int step, float grad_scale, const int32_t* found_inf,
+                     const LossScaler& scaler) {
+    AdamHyper hp;
+    hp.scaler = scaler;
     hp.lr = lr; hp.beta1 = beta1; hp.beta2 = beta2; hp.eps = eps; hp.wd = wd;
     hp.bc1 = 1.0f - powf(beta1, (float)step); hp.bc2 = 1.0f - powf(beta2, (float)step);
     hp.inv_scale = 1.0f / grad_scale; hp.found_inf = found_inf; hp.found_inf_dense = found_inf; hp.zero_grad = 1;
     hp.step_state = nullptr; hp.slot = 0;
     return hp;
 }
+
+int dense_blocks(long long n4) { return (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096); }
 
 
 // out = sum over the world slices, rank order, f32, one rounding to f16 (the direct exchange's "reduce" half).  8 values per thread.
@@ -551,6 +482,53 @@ sum_slices_kernel(const uint4* __restrict__ own, const uint4* __restrict__ stage
 
 }  // namespace
 
+int launch_field_adam(const FieldAdam& f, const LossScaler& scaler, hipStream_t stream) {
+    // n_grid == 0: the MLP blocks only (a data-parallel rank whose shard of the table is empty)
+    if (f.n_grid < 0 || f.n_density <= 0 || f.n_rgb <= 0 || f.n_partials < 0 || f.step < 1 || f.grad_scale == 0.f) return NGP_EINVAL;
+    if (f.n_grid > 0) { NGP_CHECK_PTR(f.grid_param); NGP_CHECK_PTR(f.grid_grad); NGP_CHECK_PTR(f.grid_m); NGP_CHECK_PTR(f.grid_v); }
+    NGP_CHECK_PTR(f.density_param); NGP_CHECK_PTR(f.density_m); NGP_CHECK_PTR(f.density_v);
+    NGP_CHECK_PTR(f.rgb_param); NGP_CHECK_PTR(f.rgb_m); NGP_CHECK_PTR(f.rgb_v);
+    if (f.n_partials > 0) { NGP_CHECK_PTR(f.density_partials); NGP_CHECK_PTR(f.rgb_partials); }
+    Src src = Src::F16;
+    long long n4 = (f.n_grid + 3) / 4;
+    GridPartials gp = {};
+    AdamPieces pc = {};
+    if (f.merge) {
+        const ngp_grid_partials& q = *f.merge;
+        if (q.n_levels < 0 || q.n_levels > 8 || q.value_end < 0 || q.value_end > f.n_grid || (q.value_end & 3)) return NGP_EINVAL;
+        if (q.n_levels > 0) {                                                   // (none: the plain f16 update)
+            NGP_CHECK_PTR(q.partial);
+            gp.value_end = q.value_end; gp.n_levels = q.n_levels; gp.partial = reinterpret_cast<const float2*>(q.partial);
+            for (int l = 0; l < 8; ++l) {
+                gp.offset[l] = q.offset[l < q.n_levels ? l : q.n_levels];
+                gp.k_split[l] = l < q.n_levels ? q.k_split[l] : 1;
+                gp.part_off[l] = l < q.n_levels ? q.part_off[l] : 0;
+                if (l < q.n_levels && (((q.offset[l + 1] - q.offset[l]) & 1u) || (q.part_off[l] & 1) || q.k_split[l] < 1)) return NGP_EINVAL;   // 16-byte loads of entry pairs
+            }
+            if (q.n_levels == 8) return NGP_EUNSUP;                             // offset[l + 1] of the last level would not fit the device record
+            gp.offset[q.n_levels] = q.offset[q.n_levels];
+            if (2 * (int64_t)q.offset[q.n_levels] != q.value_end) return NGP_EINVAL;
+            src = Src::F16_MERGE;
+        }
+    } else if (f.piece > 0) {
+        NGP_CHECK_PTR(f.grid_param_h);
+        pc = {(long long)f.piece, (long long)f.world * f.piece, (long long)f.rank * f.piece};
+        n4 = (long long)f.n_chunks * f.piece / 4;
+        src = Src::PIECES;
+    }
+    AdamHyper hp = adam_hyper(f.lr, f.beta1, f.beta2, f.eps, f.weight_decay, f.step, f.grad_scale, f.found_inf, scaler);
+    hp.found_inf_dense = f.found_inf_grid;
+    hp.zero_grad = f.zero_grid_grad != 0;
+    hp.step_state = f.step_state; hp.slot = (f.step - 1) & 1;
+    const AdamMlp a = {f.density_param, (h1*)f.density_param_h, f.density_partials, f.density_m, f.density_v, f.n_density, ngp_div_up(f.n_density, 32)};
+    const AdamMlp b = {f.rgb_param, (h1*)f.rgb_param_h, f.rgb_partials, f.rgb_m, f.rgb_v, f.n_rgb, ngp_div_up(f.n_rgb, 32)};
+    const dim3 grid(a.blocks + b.blocks + dense_blocks(n4));
+    auto kernel = src == Src::F16 ? adam_field_kernel<Src::F16> : src == Src::F16_MERGE ? adam_field_kernel<Src::F16_MERGE> : adam_field_kernel<Src::PIECES>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, f.grid_param, (h1*)f.grid_param_h, (void*)f.grid_grad, f.grid_m, f.grid_v,
+                       n4, (long long)f.n_grid, a, b, f.n_partials, hp, gp, pc);
+    return NGP_LAUNCH_RESULT();
+}
+
 extern "C" {
 #pragma GCC visibility push(default)
 
@@ -570,15 +548,10 @@ int ngp_adam_step(float* param, ngp_half* param_h, void* grad, int grad_is_f32, 
     if (n < 0 || step < 1 || grad_scale == 0.f) return NGP_EINVAL;
     if (n == 0) return 0;
     NGP_CHECK_PTR(param); NGP_CHECK_PTR(grad); NGP_CHECK_PTR(m); NGP_CHECK_PTR(v);
-    const AdamHyper hp = adam_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale, found_inf);
+    const AdamHyper hp = adam_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale, found_inf, take_scaler());
     const long long n4 = (n + 3) / 4;
-    const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    if (grad_is_f32)
-        hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks), dim3(256), 0, ngp_stream(stream), param, (h1*)param_h, grad, m, v,
-                           n4, (long long)n, hp);
-    else
-        hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, ngp_stream(stream), param, (h1*)param_h, grad, m, v,
-                           n4, (long long)n, hp);
+    hipLaunchKernelGGL(grad_is_f32 ? adam_kernel<true> : adam_kernel<false>, dim3(dense_blocks(n4)), dim3(256), 0, ngp_stream(stream),
+                       param, (h1*)param_h, grad, m, v, n4, (long long)n, hp);
     return NGP_LAUNCH_RESULT();
 }
 
@@ -589,34 +562,9 @@ int ngp_adam_step_partials(float* param, ngp_half* param_h, const float* partial
     if (n == 0) return 0;
     NGP_CHECK_PTR(param); NGP_CHECK_PTR(m); NGP_CHECK_PTR(v);
     if (n_partials > 0) NGP_CHECK_PTR(partials);
-    const AdamHyper hp = adam_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale, found_inf);
+    const AdamHyper hp = adam_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale, found_inf, take_scaler());
     hipLaunchKernelGGL(adam_partials_kernel, dim3(ngp_div_up(n, 32)), dim3(256), 0, ngp_stream(stream), param, (h1*)param_h, partials,
                        n_partials, m, v, n, hp);
-    return NGP_LAUNCH_RESULT();
-}
-
-static int adam_step_field_impl(float* grid_param, ngp_half* grid_param_h, ngp_half* grid_grad, float* grid_m, float* grid_v, int64_t n_grid,
-                                float* density_param, ngp_half* density_param_h, const float* density_partials, float* density_m,
-                                float* density_v, int n_density, float* rgb_param, ngp_half* rgb_param_h, const float* rgb_partials,
-                                float* rgb_m, float* rgb_v, int n_rgb, int n_partials, float lr, float beta1, float beta2, float eps,
-                                float weight_decay, int step, float grad_scale, int zero_grid_grad, const int32_t* found_inf,
-                                const int32_t* found_inf_grid, int32_t* step_state, ngp_stream_t stream) {
-    // n_grid == 0: the MLP blocks only (a data-parallel rank whose shard of the table is empty)
-    if (n_grid < 0 || n_density <= 0 || n_rgb <= 0 || n_partials < 0 || step < 1 || grad_scale == 0.f) return NGP_EINVAL;
-    if (n_grid > 0) { NGP_CHECK_PTR(grid_param); NGP_CHECK_PTR(grid_grad); NGP_CHECK_PTR(grid_m); NGP_CHECK_PTR(grid_v); }
-    NGP_CHECK_PTR(density_param); NGP_CHECK_PTR(density_m); NGP_CHECK_PTR(density_v);
-    NGP_CHECK_PTR(rgb_param); NGP_CHECK_PTR(rgb_m); NGP_CHECK_PTR(rgb_v);
-    if (n_partials > 0) { NGP_CHECK_PTR(density_partials); NGP_CHECK_PTR(rgb_partials); }
-    AdamHyper hp = adam_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale, found_inf);
-    hp.found_inf_dense = found_inf_grid;
-    hp.zero_grad = zero_grid_grad != 0;
-    hp.step_state = step_state; hp.slot = (step - 1) & 1;
-    const long long n4 = (n_grid + 3) / 4;
-    const int dense_blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    const AdamMlp a = {density_param, (h1*)density_param_h, density_partials, density_m, density_v, n_density, ngp_div_up(n_density, 32)};
-    const AdamMlp b = {rgb_param, (h1*)rgb_param_h, rgb_partials, rgb_m, rgb_v, n_rgb, ngp_div_up(n_rgb, 32)};
-    hipLaunchKernelGGL(adam_field_kernel, dim3(a.blocks + b.blocks + dense_blocks), dim3(256), 0, ngp_stream(stream), grid_param,
-                       (h1*)grid_param_h, (void*)grid_grad, grid_m, grid_v, n4, (long long)n_grid, a, b, n_partials, hp);
     return NGP_LAUNCH_RESULT();
 }
 
@@ -627,9 +575,10 @@ int ngp_adam_step_field(float* grid_param, ngp_half* grid_param_h, ngp_half* gri
                         float weight_decay, int step, float grad_scale, int zero_grid_grad, const int32_t* found_inf, int32_t* step_state,
                         ngp_stream_t stream) {
     if (n_grid <= 0) return NGP_EINVAL;
-    return adam_step_field_impl(grid_param, grid_param_h, grid_grad, grid_m, grid_v, n_grid, density_param, density_param_h, density_partials,
-                                density_m, density_v, n_density, rgb_param, rgb_param_h, rgb_partials, rgb_m, rgb_v, n_rgb, n_partials, lr,
-                                beta1, beta2, eps, weight_decay, step, grad_scale, zero_grid_grad, found_inf, found_inf, step_state, stream);
+    const FieldAdam f = {grid_param, grid_param_h, grid_grad, grid_m, grid_v, n_grid, density_param, density_param_h, density_partials, density_m,
+                         density_v, n_density, rgb_param, rgb_param_h, rgb_partials, rgb_m, rgb_v, n_rgb, n_partials, lr, beta1, beta2, eps,
+                         weight_decay, step, grad_scale, zero_grid_grad, found_inf, found_inf, step_state};
+    return launch_field_adam(f, take_scaler(), ngp_stream(stream));
 }
 
 int ngp_adam_step_field_merge(float* grid_param, ngp_half* grid_param_h, ngp_half* grid_grad, float* grid_m, float* grid_v, int64_t n_grid,
@@ -638,39 +587,11 @@ int ngp_adam_step_field_merge(float* grid_param, ngp_half* grid_param_h, ngp_hal
                               float* rgb_m, float* rgb_v, int n_rgb, int n_partials, float lr, float beta1, float beta2, float eps,
                               float weight_decay, int step, float grad_scale, const int32_t* found_inf, int32_t* step_state,
                               const ngp_grid_partials* partials, ngp_stream_t stream) {
-    if (!partials) return NGP_EINVAL;
-    const ngp_grid_partials& q = *partials;
-    if (q.n_levels < 0 || q.n_levels > 8 || q.value_end < 0 || q.value_end > n_grid || (q.value_end & 3)) return NGP_EINVAL;
-    if (q.n_levels == 0)
-        return ngp_adam_step_field(grid_param, grid_param_h, grid_grad, grid_m, grid_v, n_grid, density_param, density_param_h, density_partials, density_m,
-                                   density_v, n_density, rgb_param, rgb_param_h, rgb_partials, rgb_m, rgb_v, n_rgb, n_partials, lr, beta1, beta2, eps,
-                                   weight_decay, step, grad_scale, 0, found_inf, step_state, stream);
-    if (n_grid <= 0 || n_density <= 0 || n_rgb <= 0 || n_partials < 0 || step < 1 || grad_scale == 0.f) return NGP_EINVAL;
-    NGP_CHECK_PTR(grid_param); NGP_CHECK_PTR(grid_grad); NGP_CHECK_PTR(grid_m); NGP_CHECK_PTR(grid_v); NGP_CHECK_PTR(q.partial);
-    NGP_CHECK_PTR(density_param); NGP_CHECK_PTR(density_m); NGP_CHECK_PTR(density_v);
-    NGP_CHECK_PTR(rgb_param); NGP_CHECK_PTR(rgb_m); NGP_CHECK_PTR(rgb_v);
-    if (n_partials > 0) { NGP_CHECK_PTR(density_partials); NGP_CHECK_PTR(rgb_partials); }
-    GridPartials gp;
-    gp.value_end = q.value_end; gp.n_levels = q.n_levels; gp.partial = reinterpret_cast<const float2*>(q.partial);
-    for (int l = 0; l < 8; ++l) {
-        gp.offset[l] = q.offset[l < q.n_levels ? l : q.n_levels];
-        gp.k_split[l] = l < q.n_levels ? q.k_split[l] : 1;
-        gp.part_off[l] = l < q.n_levels ? q.part_off[l] : 0;
-        if (l < q.n_levels && (((q.offset[l + 1] - q.offset[l]) & 1u) || (q.part_off[l] & 1) || q.k_split[l] < 1)) return NGP_EINVAL;   // 16-byte loads of entry pairs
-    }
-    if (q.n_levels == 8) return NGP_EUNSUP;                                   // offset[l + 1] of the last level would not fit the device record
-    gp.offset[q.n_levels] = q.offset[q.n_levels];
-    if (2 * (int64_t)q.offset[q.n_levels] != q.value_end) return NGP_EINVAL;
-    AdamHyper hp = adam_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale, found_inf);
-    hp.zero_grad = 0;
-    hp.step_state = step_state; hp.slot = (step - 1) & 1;
-    const long long n4 = (n_grid + 3) / 4;
-    const int dense_blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    const AdamMlp a = {density_param, (h1*)density_param_h, density_partials, density_m, density_v, n_density, ngp_div_up(n_density, 32)};
-    const AdamMlp b = {rgb_param, (h1*)rgb_param_h, rgb_partials, rgb_m, rgb_v, n_rgb, ngp_div_up(n_rgb, 32)};
-    hipLaunchKernelGGL(adam_field_merge_kernel, dim3(a.blocks + b.blocks + dense_blocks), dim3(256), 0, ngp_stream(stream), grid_param,
-                       (h1*)grid_param_h, (void*)grid_grad, grid_m, grid_v, n4, (long long)n_grid, a, b, n_partials, hp, gp);
-    return NGP_LAUNCH_RESULT();
+    if (!partials || n_grid <= 0) return NGP_EINVAL;
+    const FieldAdam f = {grid_param, grid_param_h, grid_grad, grid_m, grid_v, n_grid, density_param, density_param_h, density_partials, density_m,
+                         density_v, n_density, rgb_param, rgb_param_h, rgb_partials, rgb_m, rgb_v, n_rgb, n_partials, lr, beta1, beta2, eps,
+                         weight_decay, step, grad_scale, 0, found_inf, found_inf, step_state, partials};
+    return launch_field_adam(f, take_scaler(), ngp_stream(stream));
 }
 
 int ngp_adam_step_field_shard(float* grid_param, ngp_half* grid_param_h, ngp_half* grid_grad, float* grid_m, float* grid_v, int64_t n_shard,
@@ -679,9 +600,10 @@ int ngp_adam_step_field_shard(float* grid_param, ngp_half* grid_param_h, ngp_hal
                               float* rgb_m, float* rgb_v, int n_rgb, int n_partials, float lr, float beta1, float beta2, float eps,
                               float weight_decay, int step, float grad_scale, const int32_t* found_inf_mlp,
                               const int32_t* found_inf_shard, int32_t* step_state, ngp_stream_t stream) {
-    return adam_step_field_impl(grid_param, grid_param_h, grid_grad, grid_m, grid_v, n_shard, density_param, density_param_h, density_partials,
-                                density_m, density_v, n_density, rgb_param, rgb_param_h, rgb_partials, rgb_m, rgb_v, n_rgb, n_partials, lr,
-                                beta1, beta2, eps, weight_decay, step, grad_scale, 0, found_inf_mlp, found_inf_shard, step_state, stream);
+    const FieldAdam f = {grid_param, grid_param_h, grid_grad, grid_m, grid_v, n_shard, density_param, density_param_h, density_partials, density_m,
+                         density_v, n_density, rgb_param, rgb_param_h, rgb_partials, rgb_m, rgb_v, n_rgb, n_partials, lr, beta1, beta2, eps,
+                         weight_decay, step, grad_scale, 0, found_inf_mlp, found_inf_shard, step_state};
+    return launch_field_adam(f, take_scaler(), ngp_stream(stream));
 }
 
 int ngp_adam_step_field_pieces(float* grid_param, ngp_half* grid_param_h, const ngp_half* shard_grad, float* grid_m, float* grid_v,
@@ -693,23 +615,11 @@ int ngp_adam_step_field_pieces(float* grid_param, ngp_half* grid_param_h, const 
                                const int32_t* found_inf_shard, int32_t* step_state, ngp_stream_t stream) {
     if (n_grid <= 0 || (n_grid & 15) || piece < 8 || (piece & 7) || n_chunks < 1 || n_chunks > 8 || world < 1 || rank < 0 || rank >= world) return NGP_EINVAL;
     if ((long long)n_chunks * world * piece < n_grid) return NGP_EINVAL;                   // the chunks must cover the table
-    if (n_density <= 0 || n_rgb <= 0 || n_partials < 0 || step < 1 || grad_scale == 0.f) return NGP_EINVAL;
-    NGP_CHECK_PTR(grid_param); NGP_CHECK_PTR(grid_param_h); NGP_CHECK_PTR(shard_grad); NGP_CHECK_PTR(grid_m); NGP_CHECK_PTR(grid_v);
-    NGP_CHECK_PTR(density_param); NGP_CHECK_PTR(density_m); NGP_CHECK_PTR(density_v);
-    NGP_CHECK_PTR(rgb_param); NGP_CHECK_PTR(rgb_m); NGP_CHECK_PTR(rgb_v);
-    if (n_partials > 0) { NGP_CHECK_PTR(density_partials); NGP_CHECK_PTR(rgb_partials); }
-    AdamHyper hp = adam_hyper(lr, beta1, beta2, eps, weight_decay, step, grad_scale, found_inf_mlp);
-    hp.found_inf_dense = found_inf_shard;
-    hp.zero_grad = 0;
-    hp.step_state = step_state; hp.slot = (step - 1) & 1;
-    const AdamPieces pc = {(long long)piece, (long long)world * piece, (long long)rank * piece, (long long)n_grid, n_chunks};
-    const long long n4 = (long long)n_chunks * piece / 4;
-    const int dense_blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    const AdamMlp a = {density_param, (h1*)density_param_h, density_partials, density_m, density_v, n_density, ngp_div_up(n_density, 32)};
-    const AdamMlp b = {rgb_param, (h1*)rgb_param_h, rgb_partials, rgb_m, rgb_v, n_rgb, ngp_div_up(n_rgb, 32)};
-    hipLaunchKernelGGL(adam_field_pieces_kernel, dim3(a.blocks + b.blocks + dense_blocks), dim3(256), 0, ngp_stream(stream), grid_param,
-                       (h1*)grid_param_h, (const h1*)shard_grad, grid_m, grid_v, pc, a, b, n_partials, hp);
-    return NGP_LAUNCH_RESULT();
+    const FieldAdam f = {grid_param, grid_param_h, const_cast<ngp_half*>(shard_grad), grid_m, grid_v, n_grid, density_param, density_param_h,
+                         density_partials, density_m, density_v, n_density, rgb_param, rgb_param_h, rgb_partials, rgb_m, rgb_v, n_rgb, n_partials,
+                         lr, beta1, beta2, eps, weight_decay, step, grad_scale, 0, found_inf_mlp, found_inf_shard, step_state, nullptr, piece,
+                         n_chunks, world, rank};
+    return launch_field_adam(f, take_scaler(), ngp_stream(stream));
 }
 
 int ngp_get_rays(const float* directions, const float* c2w, int n, float* rays_o, float* rays_d, ngp_stream_t stream) {
@@ -731,8 +641,8 @@ int ngp_found_inf(const void* grad, int grad_is_f32, int64_t n, int32_t* flag, i
     const long long bytes = (long long)n * (grad_is_f32 ? 4 : 2), n16 = bytes / 16;
     const int n_tail = (int)((bytes - n16 * 16) / 2);
     const int blocks = (int)((n16 + 255) / 256 < 2048 ? ((n16 + 255) / 256 > 0 ? (n16 + 255) / 256 : 1) : 2048);
-    hipLaunchKernelGGL(found_inf_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const u32x4*>(grad), n16,
-                       reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(grad) + n16 * 16), n_tail, grad_is_f32 ? 0 : 1, flag);
+    hipLaunchKernelGGL(found_inf2_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const u32x4*>(grad), n16, grad_is_f32 ? 0 : 1,
+                       nullptr, 0LL, 0, reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(grad) + n16 * 16), n_tail, flag, nullptr);
     return NGP_LAUNCH_RESULT();
 }
 
@@ -747,7 +657,7 @@ int ngp_found_inf2(const void* grad_a, int a_is_f32, int64_t n_a, const void* gr
     const long long n16 = (bytes_a + bytes_b) / 16;
     const int blocks = (int)((n16 + 255) / 256 < 2048 ? ((n16 + 255) / 256 > 0 ? (n16 + 255) / 256 : 1) : 2048);
     hipLaunchKernelGGL(found_inf2_kernel, dim3(blocks), dim3(256), 0, ngp_stream(stream), reinterpret_cast<const u32x4*>(grad_a), bytes_a / 16,
-                       a_is_f32 ? 0 : 1, reinterpret_cast<const u32x4*>(grad_b), bytes_b / 16, b_is_f32 ? 0 : 1, flag, flag_clear);
+                       a_is_f32 ? 0 : 1, reinterpret_cast<const u32x4*>(grad_b), bytes_b / 16, b_is_f32 ? 0 : 1, nullptr, 0, flag, flag_clear);
     return NGP_LAUNCH_RESULT();
 }
 
@@ -766,7 +676,7 @@ int ngp_reduce_partials(const float* partials, int n_partials, int n, float* out
     if (n == 0) return 0;
     NGP_CHECK_PTR(out);
     if (n_partials > 0) NGP_CHECK_PTR(partials);
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(ngp_div_up(n, 32)), dim3(256), 0, ngp_stream(stream), partials, n_partials, n, out);
+    hipLaunchKernelGGL(reduce_partials2_kernel, dim3(ngp_div_up(n, 32)), dim3(256), 0, ngp_stream(stream), partials, n, nullptr, 0, n_partials, out);
     return NGP_LAUNCH_RESULT();
 }
 

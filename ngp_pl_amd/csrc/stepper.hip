@@ -7,6 +7,7 @@
 // sample count of the batch's march, written by the scan kernel into pinned host memory -- polled with a deadline.
 // No device memory is allocated here; all buffers are the caller's (ngp_step_buffers).
 #include "ngp_common.h"
+#include "adam_common.h"
 #include "comm.h"
 #include <algorithm>
 #include <chrono>
@@ -612,14 +613,25 @@ int ngp_stepper_table_backward(ngp_stepper* s, int n_groups, int group, ngp_stre
     return 0;
 }
 
-// The optimizer launch enqueued next divides by this step's dynamic loss scale and writes the next step's (optim.hip: LossScaler).
-static void withdraw_scaler() { (void)ngp_adam_use_loss_scaler(nullptr, 0, 2.0f, 0.5f, 1, 1.0f, 1.0f); }
-
-static int hand_over_scaler(ngp_stepper* s) {
-    if (!s->scaler_on) return 0;
-    STEP_TRY(ngp_adam_use_loss_scaler(s->scaler_state, s->scaler_slot, s->scaler_growth, s->scaler_backoff, s->scaler_interval, s->scaler_lo, s->scaler_hi));
-    s->scaler_slot ^= 1;                 // the next step's field backward reads what this launch writes
-    return 0;
+// The field update of a step on the stepper's parameters and moments (optim.hip: launch_field_adam).  It divides by this step's
+// dynamic loss scale and writes the next step's half (adam_common.h: LossScaler), which the next field backward reads: scaler_slot
+// flips here, whether or not the launch goes out.  `pieces`: this rank's pieces of every chunk of the exchanged table (the plan
+// passed ngp_adam_step_field_pieces's checks in ngp_stepper_set_exchange).
+static int field_adam(ngp_stepper* s, const float* density_partials, const float* rgb_partials, int n_partials, float lr, int32_t step,
+                      float grad_scale, const int32_t* found_inf, const int32_t* found_inf_grid, int32_t* step_state,
+                      const ngp_grid_partials* merge, ngp_half* pieces, hipStream_t st) {
+    const ngp_stepper_config& c = s->c;
+    FieldAdam f = {c.enc_param + c.n_density, c.enc_half + c.n_density, c.grid_grad16, c.enc_m + c.n_density, c.enc_v + c.n_density, c.n_grid,
+                   c.enc_param, c.enc_half, density_partials, c.enc_m, c.enc_v, c.n_density, c.rgb_param, c.rgb_half, rgb_partials, c.rgb_m,
+                   c.rgb_v, c.n_rgb, n_partials, lr, c.beta1, c.beta2, c.eps, c.weight_decay, step, grad_scale, 0, found_inf, found_inf_grid,
+                   step_state, merge};
+    if (pieces) { f.grid_grad = pieces; f.piece = s->x.piece; f.n_chunks = s->x.n_chunks; f.world = s->comm->world; f.rank = s->comm->rank; }
+    LossScaler q = {};
+    if (s->scaler_on) {
+        q = {s->scaler_state, s->scaler_slot, s->scaler_growth, s->scaler_backoff, s->scaler_interval, s->scaler_lo, s->scaler_hi};
+        s->scaler_slot ^= 1;
+    }
+    return launch_field_adam(f, q, st);
 }
 
 // (csrc/ngp_internal.h) For an optimizer launch the CALLER enqueues (ngp_pl_amd.optim.FusedAdam behind render()'s native backward:
@@ -629,7 +641,10 @@ int ngp_stepper_before_update(ngp_stepper* s, int32_t** found_inf) {
     if (!s || !found_inf) return NGP_EINVAL;
     *found_inf = s->guard_armed ? s->guard + s->guard_parity : nullptr;
     s->guard_armed = false;
-    return hand_over_scaler(s);
+    if (!s->scaler_on) return 0;
+    STEP_TRY(ngp_adam_use_loss_scaler(s->scaler_state, s->scaler_slot, s->scaler_growth, s->scaler_backoff, s->scaler_interval, s->scaler_lo, s->scaler_hi));
+    s->scaler_slot ^= 1;                 // the next step's field backward reads what that launch writes
+    return 0;
 }
 
 int ngp_stepper_update(ngp_stepper* s, float lr, int32_t step, float grad_scale, const float* density_partials,
@@ -648,15 +663,8 @@ int ngp_stepper_update(ngp_stepper* s, float lr, int32_t step, float grad_scale,
     if (n_partials < 1) return NGP_EINVAL;
     if (found_inf == nullptr && s->guard_armed && density_partials == b.partials) found_inf = s->guard + s->guard_parity;    // this step's own field backward
     s->guard_armed = false;
-    STEP_TRY(hand_over_scaler(s));
-    {
-        const int rc_adam = ngp_adam_step_field(c.enc_param + c.n_density, c.enc_half + c.n_density, c.grid_grad16, c.enc_m + c.n_density, c.enc_v + c.n_density, c.n_grid,
-                                 c.enc_param, c.enc_half, density_partials, c.enc_m, c.enc_v, c.n_density,
-                                 c.rgb_param, c.rgb_half, rgb_partials, c.rgb_m, c.rgb_v, c.n_rgb,
-                                 n_partials, lr, c.beta1, c.beta2, c.eps, c.weight_decay, step, grad_scale, 0, found_inf, step_state, main_stream);
-        withdraw_scaler();                       // (consumed by a launch that went out; withdrawn if validation refused it)
-        if (rc_adam) return rc_adam;
-    }
+    STEP_TRY(field_adam(s, density_partials, rgb_partials, n_partials, lr, step, grad_scale, found_inf, found_inf, step_state, nullptr, nullptr,
+                        ngp_stream(main_stream)));
     mark(s, 8, ngp_stream(main_stream));
     STEP_TRY(march_next_if_at(s, AT_ADAM));
     return 0;
@@ -674,23 +682,12 @@ int ngp_stepper_backward_update(ngp_stepper* s, float lr, int32_t step, float gr
     HostTimer host_timer(&s->t_enqueue);
     if (!c.enc_param || !c.enc_m || !c.enc_v || !c.rgb_param || !c.rgb_m || !c.rgb_v) return NGP_EINVAL;
     ngp_grid_partials gp;
-    const int64_t n_streamed = c.n_grid;                         // the whole table's gradient is applied by the streaming launch
-    {
-        const int rc = table_backward_group(s, 1, 0, &gp, main_stream);
-        if (rc) return rc;
-    }
+    STEP_TRY(table_backward_group(s, 1, 0, &gp, main_stream));
     mark(s, 7, ngp_stream(main_stream));
     STEP_TRY(march_next_if_at(s, AT_HASHGRID_BWD));
-    STEP_TRY(hand_over_scaler(s));
-    {
-        const int rc_adam = ngp_adam_step_field_merge(c.enc_param + c.n_density, c.enc_half + c.n_density, c.grid_grad16, c.enc_m + c.n_density, c.enc_v + c.n_density, n_streamed,
-                                       c.enc_param, c.enc_half, b.partials, c.enc_m, c.enc_v, c.n_density,
-                                       c.rgb_param, c.rgb_half, b.partials + (size_t)s->n_part * c.n_density, c.rgb_m, c.rgb_v, c.n_rgb,
-                                       s->n_part, lr, c.beta1, c.beta2, c.eps, c.weight_decay, step, grad_scale,
-                                       s->guard_armed ? s->guard + s->guard_parity : nullptr, step_state, &gp, main_stream);
-        withdraw_scaler();                       // (consumed by a launch that went out; withdrawn if validation refused it)
-        if (rc_adam) return rc_adam;
-    }
+    const int32_t* guard = s->guard_armed ? s->guard + s->guard_parity : nullptr;
+    STEP_TRY(field_adam(s, b.partials, b.partials + (size_t)s->n_part * c.n_density, s->n_part, lr, step, grad_scale, guard, guard, step_state, &gp,
+                        nullptr, ngp_stream(main_stream)));
     s->guard_armed = false;
     mark(s, 8, ngp_stream(main_stream));
     STEP_TRY(march_next_if_at(s, AT_ADAM));
@@ -826,16 +823,7 @@ int ngp_stepper_tail(ngp_stepper* s, float lr, int32_t step, float grad_scale, n
     if (x.mode >= 1) {
         STEP_TRY(ngp_found_inf2(x.small, 1, n_small, nullptr, 0, 0, mlp_cur, mlp_nxt, cst));
         STEP_TRY(ngp_found_inf2(x.shard16, 0, (int64_t)x.n_chunks * x.piece, nullptr, 0, 0, grid_cur, grid_nxt, cst));
-        STEP_TRY(hand_over_scaler(s));
-        {
-            const int rc_adam = ngp_adam_step_field_pieces(c.enc_param + c.n_density, c.enc_half + c.n_density, x.shard16, c.enc_m + c.n_density, c.enc_v + c.n_density,
-                                            c.n_grid, x.piece, x.n_chunks, comm->world, comm->rank,
-                                            c.enc_param, c.enc_half, x.small, c.enc_m, c.enc_v, c.n_density,
-                                            c.rgb_param, c.rgb_half, x.small + c.n_density, c.rgb_m, c.rgb_v, c.n_rgb,
-                                            1, lr, c.beta1, c.beta2, c.eps, c.weight_decay, step, grad_scale, mlp_cur, grid_cur, x.step_state, cst);
-            withdraw_scaler();                       // (consumed by a launch that went out; withdrawn if validation refused it)
-            if (rc_adam) return rc_adam;
-        }
+        STEP_TRY(field_adam(s, x.small, x.small + c.n_density, 1, lr, step, grad_scale, mlp_cur, grid_cur, x.step_state, nullptr, x.shard16, cs));
         // the updated f16 table: every rank's pieces to every rank, in place (one RCCL group: one launch for all chunks)
         if (x.mode == 2) {
             STEP_TRY(ngp_comm_all_gather_direct(comm, x.table_padded, x.piece, NGP_COMM_F16, cst));
@@ -852,15 +840,7 @@ int ngp_stepper_tail(ngp_stepper* s, float lr, int32_t step, float grad_scale, n
     } else {
         // one flag for everything (all ranks hold the same sums): GradScaler's whole-step decision
         STEP_TRY(ngp_found_inf2(x.grad_padded, 0, padded, x.small, 1, n_small, mlp_cur, mlp_nxt, cst));
-        STEP_TRY(hand_over_scaler(s));
-        {
-            const int rc_adam = ngp_adam_step_field(c.enc_param + c.n_density, c.enc_half + c.n_density, c.grid_grad16, c.enc_m + c.n_density, c.enc_v + c.n_density, c.n_grid,
-                                     c.enc_param, c.enc_half, x.small, c.enc_m, c.enc_v, c.n_density,
-                                     c.rgb_param, c.rgb_half, x.small + c.n_density, c.rgb_m, c.rgb_v, c.n_rgb,
-                                     1, lr, c.beta1, c.beta2, c.eps, c.weight_decay, step, grad_scale, 0, mlp_cur, x.step_state, cst);
-            withdraw_scaler();                       // (consumed by a launch that went out; withdrawn if validation refused it)
-            if (rc_adam) return rc_adam;
-        }
+        STEP_TRY(field_adam(s, x.small, x.small + c.n_density, 1, lr, step, grad_scale, mlp_cur, mlp_cur, x.step_state, nullptr, nullptr, cs));
     }
     if (timing) { STEP_HIP(hipEventRecord(s->ev_x1, cs)); s->x_times_set = true; }
     // (4) the one wait of the main stream: the next forward, the occupancy update and the next tail's memsets read / write what

@@ -335,18 +335,12 @@ class ShardedExchange(GradientExchange):
 
     def _adam_kernel(self, lr, step, grad_scale, nat, flag_mlp, flag_shard, stream_handle):
         from ._lib import call, ptr, stream
-        tr = self._trainer
-        m = self.model
-        enc, net = m.xyz_encoder, m.rgb_net
-        (em, ev), (rm, rv) = tr.opt.moments("enc"), tr.opt.moments("rgb")
-        b1, b2 = tr.opt.betas
-        ne = enc.n_mlp
-        p_enc, p_half, p_m, p_v = enc.params.data_ptr(), self._h_big.data_ptr(), em.data_ptr(), ev.data_ptr()
+        opt = self._trainer.opt
+        enc, net = self.model.xyz_encoder, self.model.rgb_net
         sq = stream_handle if stream_handle is not None else stream()
-        mlp = (p_enc, p_half, ptr(nat["density_partials"]), p_m, p_v, ne,
-               net.params.data_ptr(), net._half.t.data_ptr(), ptr(nat["rgb_partials"]), rm.data_ptr(), rv.data_ptr(), net.params.numel(),
-               nat["n_partials"], lr, b1, b2, tr.opt.eps, tr.opt.weight_decay, step, grad_scale, ptr(flag_mlp), ptr(flag_shard),
-               tr.opt.step_state(flag_mlp), sq)
+        mlp = opt.field_mlp_args(nat, self._h_big.data_ptr(), lr, step, grad_scale)
+        p_enc, p_half, _, p_m, p_v, ne = mlp[:6]
+        mlp += (ptr(flag_mlp), ptr(flag_shard), opt.step_state(flag_mlp), sq)
         if self.n_chunks == 1:
             lo, n = self.lo, self.hi - self.lo
             # (a rank whose shard is empty -- rank * shard_len >= n_grid: small tables, large worlds -- passes n = 0: the MLP blocks only)

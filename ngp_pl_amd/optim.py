@@ -259,13 +259,23 @@ class FusedAdam(torch.optim.Optimizer):
             mod._half.get(p)
         return mod._half.t
 
+    def field_mlp_args(self, nat, p_half, lr, step, grad_scale):
+        """The density / rgb half of the ngp_adam_step_field* argument list, from the density MLP block to grad_scale: both MLP
+        blocks with the partial rows of the native record `nat`, n_partials and the hyper-parameters.  p_half: address of the f16
+        copy of xyz_encoder.params.  Items 0, 1, 3, 4, 5 (f32 / f16 / m / v base addresses, density MLP size) also locate the grid
+        block, which follows the density MLP in the encoder's tensors."""
+        enc, net = self.model.xyz_encoder, self.model.rgb_net
+        (m, v), (rm, rv) = self.moments("enc"), self.moments("rgb")
+        b1, b2 = self.betas
+        # raw pointers (a tensor slice costs ~4 us of host time, the caller passes 6 of them by arithmetic)
+        return (enc.params.data_ptr(), p_half, ptr(nat["density_partials"]), m.data_ptr(), v.data_ptr(), enc.n_mlp,
+                net.params.data_ptr(), net._half.t.data_ptr(), ptr(nat["rgb_partials"]), rm.data_ptr(), rv.data_ptr(), net.params.numel(),
+                nat["n_partials"], lr, b1, b2, self.eps, self.weight_decay, step, grad_scale)
+
     def _step_native(self, nat, grad_scale, found_inf, stream_handle):
         model = self.model
         enc, net = model.xyz_encoder, model.rgb_net
         self.t += 1
-        group = self.param_groups[0]
-        lr = group["lr"]
-        b1, b2 = group["betas"]
         total_scale = nat["scale"] * grad_scale
         sq = stream_handle if stream_handle is not None else stream()
         h = nat.get("stepper")
@@ -277,19 +287,13 @@ class FusedAdam(torch.optim.Optimizer):
             call("ngp_stepper_before_update", h, C.byref(fi))
             if found_inf is None and fi.value:
                 found_inf = _FlagRef(fi.value)
-        m, v = self.moments("enc")
-        rm, rv = self.moments("rgb")
-        ne = enc.n_mlp
-        # raw pointers by arithmetic (a tensor slice costs ~4 us of host time, this call passes 6 of them)
-        p_enc, p_half, p_m, p_v = enc.params.data_ptr(), enc._half.t.data_ptr(), m.data_ptr(), v.data_ptr()
+        mlp = self.field_mlp_args(nat, enc._half.t.data_ptr(), self.lr, self.t, total_scale)
+        p_enc, p_half, _, p_m, p_v, ne = mlp[:6]
         guard = device_guard(enc.params.device) if stream_handle is None else contextlib.nullcontext()     # a raw stream handle names its device
         try:
             with guard:
-                call("ngp_adam_step_field", p_enc + 4 * ne, p_half + 2 * ne, ptr(nat["grid16"]), p_m + 4 * ne, p_v + 4 * ne, enc.n_grid,
-                     p_enc, p_half, ptr(nat["density_partials"]), p_m, p_v, ne,
-                     net.params.data_ptr(), net._half.t.data_ptr(), ptr(nat["rgb_partials"]), rm.data_ptr(), rv.data_ptr(), net.params.numel(),
-                     nat["n_partials"], lr, b1, b2, group["eps"], group["weight_decay"], self.t, total_scale, 0, ptr(found_inf),
-                     self.step_state(found_inf), sq)      # 0: every table backward of this package overwrites the gradient
+                call("ngp_adam_step_field", p_enc + 4 * ne, p_half + 2 * ne, ptr(nat["grid16"]), p_m + 4 * ne, p_v + 4 * ne, enc.n_grid, *mlp,
+                     0, ptr(found_inf), self.step_state(found_inf), sq)      # 0: every table backward of this package overwrites the gradient
         finally:
             if h is not None:                         # (a launch that went out has consumed the hand-over; one that raised must not leave it behind)
                 call("ngp_adam_use_loss_scaler", None, 0, 2.0, 0.5, 1, 1.0, 1.0)

@@ -543,3 +543,30 @@ def test_loss_scaler_backs_off_on_overflow_and_grows_after_clean_steps():
     assert any(b > a for a, b in zip(seen, seen[1:]))                            # (growth happened)
     enc, net = m.xyz_encoder, m.rgb_net
     assert bool(torch.isfinite(enc.params).all()) and bool(torch.isfinite(net.params).all())
+
+
+def test_merge_inside_adam_equals_table_backward_then_update():
+    """ngp_stepper_backward_update (the dense levels' K partial tables summed inside the Adam launch) against the two-call path
+    (table backward with its merge kernel, then ngp_stepper_update; an MLP-gradient hook forces it): parameters, f16 working copies
+    and both moments are bit-identical after 3 steps on batches the binned backward takes."""
+    from ngp_pl_amd.networks import NGP
+    from ngp_pl_amd.trainer import Trainer
+    dev = torch.device("cuda")
+    ro, rd, gt = _scaler_batch(dev)
+
+    def run(hooked):
+        torch.manual_seed(3)
+        m = NGP(scale=0.5).to(dev)
+        tr = Trainer(m, loss_scaler=False)
+        if hooked:
+            tr.mlp_grad_hook = lambda: None
+            tr.opt.ensure_step_state(0)          # both paths take the bias correction from the device-side count
+        for _ in range(3):
+            tr.step(ro, rd, gt)
+            assert 0 < tr.last["rm_samples"] <= tr.buffers(ro.shape[0]).bin_max
+        enc, net = m.xyz_encoder, m.rgb_net
+        return [p.clone() for p in (enc.params.detach(), net.params.detach(), enc._half.get(enc.params), net._half.get(net.params),
+                                    *tr.opt.moments("enc"), *tr.opt.moments("rgb"))]
+    fused, two_call = run(False), run(True)
+    for a, b in zip(fused, two_call):
+        assert torch.equal(a, b)

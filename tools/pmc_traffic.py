@@ -26,7 +26,7 @@ STAGES = {   # stage of bench.py's roofline block -> kernels of that library cal
 
 def matches(name, kernels):
     """Does the (possibly mangled) kernel name belong to one of `kernels`?  The name must START with it, or follow the length prefix of
-    an Itanium-mangled name (..._112merge_kernelE...): `merge_kernel` must not claim `adam_field_merge_kernel`."""
+    an Itanium-mangled name (..._112merge_kernelE...): `merge_kernel` must not claim a kernel whose name only ends in it."""
     return any(re.search(r"(?:^|\d)%s" % re.escape(k), name) for k in kernels)
 
 

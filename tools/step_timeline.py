@@ -7,7 +7,7 @@ import sys
 
 def short(name):
     name = re.sub(r"\(anonymous namespace\)::", "", name)
-    m = re.match(r"_ZN12_GLOBAL__N_1\d+([A-Za-z_0-9]+?)(I[LbEi0-9]+E)?Ev?P", name)
+    m = re.match(r"_ZN12_GLOBAL__N_1\d+([A-Za-z_0-9]+?)(I(?:[LbEi0-9]|LNS_\d+SrcE)+E)?Ev?P", name)
     if m:
         return m.group(1) + (m.group(2) or "")
     name = re.sub(r"^void ", "", name)
