@@ -16,6 +16,7 @@
 
 #include <cstdlib>
 #include <chrono>
+#include <type_traits>
 #include "ngp_common.h"
 
 #define NGP_SQRT3 1.73205080757f
@@ -373,6 +374,41 @@ __device__ __forceinline__ Ray load_ray(const float* __restrict__ rays_o, const 
     return ray;
 }
 
+// One packed sample: position (march_probe's own expression, x = fmaf(t, d, o)), direction, t and step.
+__device__ __forceinline__ void write_sample(float* xyzs, float* dirs, float* deltas, float* ts,
+                                             size_t o, float ox, float oy, float oz, float dx, float dy, float dz, float t, float dt) {
+    xyzs[3 * o] = fmaf(t, dx, ox); xyzs[3 * o + 1] = fmaf(t, dy, oy); xyzs[3 * o + 2] = fmaf(t, dz, oz);
+    dirs[3 * o] = dx; dirs[3 * o + 1] = dy; dirs[3 * o + 2] = dz;
+    ts[o] = t; deltas[o] = dt;
+}
+
+// The reference's test-time loop (raymarching.cu:353-403), one thread per ray: probe the cell at t, `emit(s, t, dt)` and step by dt
+// when it is occupied, else skip to the lattice point behind it; stop at the far hit t2 or behind the cap-th sample.  Returns the
+// number of samples; t_resume moves only past emitted samples (raymarching.cu:390).  block_any / hop_slack: march_probe's block hops.
+// tally: probe counters for the diagnostics build (frame loop only); counters nobody reads afterwards are dead code, so the plain build
+// pays nothing for them.
+struct ProbeTally { int probes = 0, hops_short = 0, hops_long = 0; };     // hops of at most / more than 8 lattice steps (a cell's diagonal is 8 steps long)
+template <bool SIMPLE, typename Emit>
+__device__ __forceinline__ int march_serial_walk(const Ray& ray, const MarchParams& p, float t, float t2, int cap, float& t_resume, Emit emit,
+                                                 const uint32_t* block_any = nullptr, float hop_slack = 0.0f, ProbeTally* tally = nullptr) {
+    int s = 0, iters = 0;
+    t_resume = t;
+    while (t < t2 && s < cap) {
+        if (++iters > MARCH_ITER_CAP) { atomicAdd(&g_march_guard[2], 1u); t_resume = t2; break; }
+        if (tally) ++tally->probes;
+        float x, y, z, dt, t_next;
+        if (march_probe<SIMPLE>(ray, p, t, x, y, z, dt, t_next, nullptr, block_any, hop_slack)) {
+            emit(s, t, dt);
+            t += dt; ++s;
+            t_resume = t;
+        } else {
+            if (tally) { if (t_next - t > 8.5f * p.dt_lo) ++tally->hops_long; else ++tally->hops_short; }
+            t = t_next;
+        }
+    }
+    return s;
+}
+
 // Pass 1 of train marching (raymarching.cu:184-234): one march per ray, t of every emitted sample goes to the ray's scratch row.
 // The reference's loop is a chain of dependent bitfield loads with per-ray trip counts from 0 to ~600 (a serial-chain kernel, 16 rays
 // per wave, took 280-330 us per 8192-ray batch: round 1; removed in round 5, tests/test_march_parallel_proto_cpu.py keeps the numpy
@@ -417,7 +453,7 @@ __device__ __forceinline__ bool lattice_tile_const_dt(float t_start, float dt, i
 }
 
 // ONE WAVE PER RAY, bit-identical to the serial loop.  The loop visits a subsequence of one
-// fixed sequence per ray, T[0] = t1, T[j+1] = T[j] + calc_dt(T[j]): an occupied cell advances by one element, an empty
+// fixed sequence per ray, T[0] = t_start, T[j+1] = T[j] + calc_dt(T[j]): an occupied cell advances by one element, an empty
 // cell by k >= 1 elements (the do-while of the skip).  Per tile of 64 elements the wave
 //   1. generates the 64 elements (a chain of adds, no memory) -- lane j keeps T[j];
 //   2. probes all 64 candidates in parallel (march_probe, the serial kernel's own arithmetic): occupancy bit and, for
@@ -428,45 +464,24 @@ __device__ __forceinline__ bool lattice_tile_const_dt(float t_start, float dt, i
 //      scalar unit is shared by the CU's four SIMDs: one read per skipped cell made the kernel SALU-bound).  Candidates the
 //      serial loop jumps over are never emitted, whatever their own bit says (next to a voxel face the computed skip
 //      target can reach a rounding error into the neighbour cell);
-//   4. writes the visited occupied candidates' t to the ray's scratch row (coalesced, ranked by popcount).
+//   4. hands the visited occupied candidates' t to `store(index, t)`, ranked by popcount (consecutive lanes, consecutive indices).
 // A skip that leaves the tile carries its landing value into the following tiles.  tools/march_parallel_proto.py is
 // this algorithm in numpy against the oracle.  8192 rays = 8192 waves instead of 512 serial chains of dependent loads.
-// PROLOGUE (the native stepper's march): the wave also forms its ray's hit interval and jitter -- render()'s prologue
-// (rendering.py:27-29: one box, one hit, near clamp; custom_functions.py:83: the jitter draw), the arithmetic of ray_aabb_near_kernel
-// -- instead of reading them from a launch of their own, and leaves them in hits_out / noise_out for whoever reads them later.
-struct MarchPrologue { const float* center; const float* half_size; float near_distance; uint32_t seed_lo, seed_hi; float* hits_out; float* noise_out; };
-template <bool SIMPLE, bool PROLOGUE>
-__global__ void __launch_bounds__(256)
-march_train_count_wave_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-                              const float* __restrict__ hits_t, const float* __restrict__ noise,
-                              MarchParams p, int max_samples, int n_rays,
-                              int64_t* __restrict__ rays_a, float* __restrict__ t_scratch, int32_t* __restrict__ counts, MarchPrologue pro) {
-    // the ray index is wave-uniform; saying so keeps the ray, its hit interval and the whole tile walk on the scalar unit
-    const int r = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-    const int lane = threadIdx.x & 63;
-    if (r >= n_rays) return;
-    const Ray ray = load_ray(rays_o, rays_d, r);
-    float t1, t2, jitter;
-    if (PROLOGUE) {
-        const float2 t = aabb_hit(ray.ox, ray.oy, ray.oz, ray.ix, ray.iy, ray.iz, pro.center[0], pro.center[1], pro.center[2],
-                                  pro.half_size[0], pro.half_size[1], pro.half_size[2]);
-        t1 = -1.0f; t2 = -1.0f;
-        if (t.y > 0) { t1 = fmaxf(t.x, 0.0f); t2 = t.y; }
-        if (t1 >= 0 && t1 < pro.near_distance) t1 = pro.near_distance;
-        jitter = (float)(ngp_pcg_hash(ngp_rng_key(pro.seed_lo, pro.seed_hi, (uint32_t)r)) >> 8) * (1.0f / 16777216.0f);
-        if (lane == 0) { reinterpret_cast<float2*>(pro.hits_out)[r] = make_float2(t1, t2); pro.noise_out[r] = jitter; }
-    } else {
-        t1 = hits_t[2 * r]; t2 = hits_t[2 * r + 1]; jitter = noise[r];
-    }
-    if (t1 >= 0) t1 = fmaf(calc_dt(t1, p), jitter, t1);
-    float* __restrict__ row = t_scratch + (size_t)r * max_samples;
+// Both wave-per-ray kernels (train count, frame loop) walk here; ray, t_start, t2, cap, ray_id are wave-uniform.  The ray stops behind
+// its cap-th sample like the serial loops (`N_samples < max_samples`, `s < N`); returns the number of samples stored.  `store` is a
+// functor, not a float*: the train kernel's row is global memory, the frame kernel's is LDS, and the store keeps its address space
+// only while the compiler sees the array itself.  ray_id is what the tile-cap guard records in g_march_guard[3].
+// Valid prefix: `mine < t2` alone.  The reference's train loop also asks `0 <= t` (raymarching.cu:204): the train kernel enters with
+// t_start >= 0 only and every later element is t_start plus steps >= dt_lo > 0, so no lane is ever below 0 there.  The frame loop has
+// no such clause (raymarching.cu:367) and always enters: a ray that missed the box has hits (-1, -1) and no valid lane.
+template <bool SIMPLE, typename Store>
+__device__ __forceinline__ int march_tile_walk(const Ray& ray, const MarchParams& p, float t_start, float t2, int cap, int lane,
+                                               unsigned int ray_id, Store store) {
     int n = 0;
-    float t_start = t1;
     float pending = -1.0f;                              // landing value of a skip that left the previous tile (< 0: none)
-    bool done = !(t1 >= 0);
     int tiles = 0;
-    while (!done) {
-        if (++tiles > MARCH_TILE_CAP) { if (lane == 0) { atomicAdd(&g_march_guard[1], 1u); g_march_guard[3] = (unsigned)r + 1u; } break; }
+    for (;;) {
+        if (++tiles > MARCH_TILE_CAP) { if (lane == 0) { atomicAdd(&g_march_guard[1], 1u); g_march_guard[3] = ray_id + 1u; } break; }
         // 1. the tile's elements: closed form for the constant step (lattice_tile_const_dt), else the chain of 64 adds
         float mine = t_start, t_end = t_start;
         if (!(SIMPLE && lattice_tile_const_dt(t_start, p.dt_lo, lane, mine, t_end))) {
@@ -479,7 +494,7 @@ march_train_count_wave_kernel(const float* __restrict__ rays_o, const float* __r
             }
             t_end = tt;                                 // T[64]: first element of the next tile
         }
-        const int nvalid = __popcll(__ballot(0 <= mine && mine < t2));        // the sequence increases: valid lanes are a prefix
+        const int nvalid = __popcll(__ballot(mine < t2));                      // the sequence increases: valid lanes are a prefix
         const int entry = pending >= 0 ? __popcll(__ballot(mine < pending)) : 0;
         if (entry >= 64) {                              // the carried skip jumps over the whole tile
             if (nvalid < 64) break;                     // ... and over the end of the ray
@@ -490,8 +505,7 @@ march_train_count_wave_kernel(const float* __restrict__ rays_o, const float* __r
         float x, y, z, dt, t_next = 0.f;
         int k = 1;
         const bool occ = march_probe<SIMPLE>(ray, p, mine, x, y, z, dt, t_next, &k);
-        const unsigned long long occ_mask = __ballot(occ);
-        const unsigned long long empty_mask = ~occ_mask;
+        const unsigned long long empty_mask = ~__ballot(occ);
         // 3a. empty lanes: where does the chain of skips that starts here end?  Pointer doubling on the vector unit over
         //     packed (last empty lane of the chain << 8 | landing lane): after r rounds a lane knows the end of a chain of 2^r
         //     skips, so 6 rounds close every chain of a 64-lane tile (a skip advances by >= 1); rounds stop as soon as no lane's
@@ -534,18 +548,53 @@ march_train_count_wave_kernel(const float* __restrict__ rays_o, const float* __r
             if (nvalid < 64 && u >= nvalid) { finished = true; break; }             // the run (or the empty lane behind it) reaches the far hit
             v = u;                                                                    // 64: the tile ends inside a run; else the empty lane behind the run
         }
-        // 4. write out, capped at max_samples like the serial loop's N_samples < max_samples
-        const int room = max_samples - n;
+        // 4. hand over, capped
+        const int room = cap - n;
         const bool my = (emit >> lane) & 1ull;
         const int rank = __popcll(emit & ((1ull << lane) - 1ull));
-        if (my && rank < room) row[n + rank] = mine;
+        if (my && rank < room) store(n + rank, mine);
         const int cnt = __popcll(emit);
         n += cnt < room ? cnt : room;
-        if (finished || n >= max_samples) break;
+        if (finished || n >= cap) break;
         pending = next_pending;
         if (pending >= 0 && !(pending < t2)) break;     // the skip lands beyond the far hit
         t_start = t_end;
     }
+    return n;
+}
+
+// Pass 1 of train marching, one wave per ray (march_tile_walk); the samples' t go to the ray's scratch row (coalesced).
+// PROLOGUE (the native stepper's march): the wave also forms its ray's hit interval and jitter -- render()'s prologue
+// (rendering.py:27-29: one box, one hit, near clamp; custom_functions.py:83: the jitter draw), the arithmetic of ray_aabb_near_kernel
+// -- instead of reading them from a launch of their own, and leaves them in hits_out / noise_out for whoever reads them later.
+struct MarchPrologue { const float* center; const float* half_size; float near_distance; uint32_t seed_lo, seed_hi; float* hits_out; float* noise_out; };
+template <bool SIMPLE, bool PROLOGUE>
+__global__ void __launch_bounds__(256)
+march_train_count_wave_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                              const float* __restrict__ hits_t, const float* __restrict__ noise,
+                              MarchParams p, int max_samples, int n_rays,
+                              int64_t* __restrict__ rays_a, float* __restrict__ t_scratch, int32_t* __restrict__ counts, MarchPrologue pro) {
+    // the ray index is wave-uniform; saying so keeps the ray, its hit interval and the whole tile walk on the scalar unit
+    const int r = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int lane = threadIdx.x & 63;
+    if (r >= n_rays) return;
+    const Ray ray = load_ray(rays_o, rays_d, r);
+    float t1, t2, jitter;
+    if (PROLOGUE) {
+        const float2 t = aabb_hit(ray.ox, ray.oy, ray.oz, ray.ix, ray.iy, ray.iz, pro.center[0], pro.center[1], pro.center[2],
+                                  pro.half_size[0], pro.half_size[1], pro.half_size[2]);
+        t1 = -1.0f; t2 = -1.0f;
+        if (t.y > 0) { t1 = fmaxf(t.x, 0.0f); t2 = t.y; }
+        if (t1 >= 0 && t1 < pro.near_distance) t1 = pro.near_distance;
+        jitter = (float)(ngp_pcg_hash(ngp_rng_key(pro.seed_lo, pro.seed_hi, (uint32_t)r)) >> 8) * (1.0f / 16777216.0f);
+        if (lane == 0) { reinterpret_cast<float2*>(pro.hits_out)[r] = make_float2(t1, t2); pro.noise_out[r] = jitter; }
+    } else {
+        t1 = hits_t[2 * r]; t2 = hits_t[2 * r + 1]; jitter = noise[r];
+    }
+    if (t1 >= 0) t1 = fmaf(calc_dt(t1, p), jitter, t1);
+    float* __restrict__ row = t_scratch + (size_t)r * max_samples;
+    int n = 0;
+    if (t1 >= 0) n = march_tile_walk<SIMPLE>(ray, p, t1, t2, max_samples, lane, (unsigned int)r, [row](int i, float t) { row[i] = t; });
     if (lane == 0) {
         rays_a[3 * (size_t)r] = r;
         rays_a[3 * (size_t)r + 2] = n;
@@ -658,11 +707,7 @@ march_train_write_kernel(const float* __restrict__ rays_o, const float* __restri
     const float* __restrict__ row = t_scratch + (size_t)r * max_samples;
     for (int k = lane; k < n; k += 64) {
         const float t = row[k];
-        const size_t s = (size_t)start + k;
-        xyzs[3 * s] = fmaf(t, dx, ox); xyzs[3 * s + 1] = fmaf(t, dy, oy); xyzs[3 * s + 2] = fmaf(t, dz, oz);
-        dirs[3 * s] = dx; dirs[3 * s + 1] = dy; dirs[3 * s + 2] = dz;
-        ts[s] = t;
-        deltas[s] = calc_dt(t, p);
+        write_sample(xyzs, dirs, deltas, ts, (size_t)start + k, ox, oy, oz, dx, dy, dz, t, calc_dt(t, p));
     }
 }
 
@@ -679,33 +724,14 @@ march_test_kernel(const float* __restrict__ rays_o, const float* __restrict__ ra
     if (n >= n_alive) return;
     const size_t r = (size_t)alive[n];
     const Ray ray = load_ray(rays_o, rays_d, r);
-    float t = hits_t[2 * r];
-    const float t2 = hits_t[2 * r + 1];
     const size_t base = (size_t)n * n_samples;
-    int s = 0, iters = 0;
-    float t_resume = t;
-    while (t < t2 && s < n_samples) {
-        if (++iters > MARCH_ITER_CAP) { atomicAdd(&g_march_guard[2], 1u); t_resume = t2; break; }
-        float x, y, z, dt, t_next;
-        if (march_probe<SIMPLE>(ray, p, t, x, y, z, dt, t_next)) {
-            const size_t o = base + s;
-            xyzs[3 * o] = x; xyzs[3 * o + 1] = y; xyzs[3 * o + 2] = z;
-            dirs[3 * o] = ray.dx; dirs[3 * o + 1] = ray.dy; dirs[3 * o + 2] = ray.dz;
-            ts[o] = t; deltas[o] = dt;
-            t += dt; ++s;
-            t_resume = t;           // raymarching.cu:390: stored after every emitted sample only
-        } else {
-            t = t_next;
-        }
-    }
+    float t_resume;
+    const int s = march_serial_walk<SIMPLE>(ray, p, hits_t[2 * r], hits_t[2 * r + 1], n_samples, t_resume, [&](int k, float t, float dt) {
+        write_sample(xyzs, dirs, deltas, ts, base + k, ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, t, dt);
+    });
     if (s > 0) hits_t[2 * r] = t_resume;
     n_eff[n] = s;
-    for (int k = s; k < n_samples; ++k) {
-        const size_t o = base + k;
-        xyzs[3 * o] = 0.f; xyzs[3 * o + 1] = 0.f; xyzs[3 * o + 2] = 0.f;
-        dirs[3 * o] = 0.f; dirs[3 * o + 1] = 0.f; dirs[3 * o + 2] = 0.f;
-        ts[o] = 0.f; deltas[o] = 0.f;
-    }
+    for (int k = s; k < n_samples; ++k) write_sample(xyzs, dirs, deltas, ts, base + k, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f);      // padding: eight zeros
 }
 
 // Alive-ray compaction of the test-time loop (`alive_indices[alive_indices>=0]`,
@@ -725,9 +751,7 @@ compact_alive_kernel(const int64_t* __restrict__ alive_in, const int32_t* __rest
     base = __shfl(base, 0, 64);
     if (keep) alive_out[base + __popcll(m & ((1ull << lane) - 1ull))] = a;
     if (total != nullptr) {
-        int e = (i < n && n_eff != nullptr) ? n_eff[i] : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
+        const int e = ngp_wave_sum_i32((i < n && n_eff != nullptr) ? n_eff[i] : 0);
         if (lane == 0 && e) atomicAdd(reinterpret_cast<unsigned long long*>(total), (unsigned long long)e);
     }
 }
@@ -794,6 +818,23 @@ render_begin_kernel(const float* __restrict__ hits_in, int n_rays, float* __rest
     if (tid == 0) *total = 0ull;
 }
 
+// What both frame marchers open with: this iteration's alive count and N_samples (rendering.py:65-72), at most nmax per ray, published
+// to the plan by thread 0 of workgroup 0.  rendering.py:65 `while samples < max_samples`: `samples` grows by N per iteration
+// (use_samples_done).  With a probe cap a ray can advance by fewer than N samples per iteration, so that mode budgets the samples per
+// ray instead (emitted[r]); both bound a ray to max_samples (+ at most one chunk).  Returns (n_alive, N).
+__device__ __forceinline__ int2 render_plan_step(RenderPlan* __restrict__ plan, int n_rays, int chunk_scale, int min_samples, int max_samples_total,
+                                                 int nmax, bool use_samples_done) {
+    const int done = use_samples_done ? plan->samples_done : 0;
+    const int n_alive = (done < max_samples_total) ? plan->n_alive_raw : 0;
+    int N = 0;
+    if (n_alive > 0) N = max(min((int)(((long long)chunk_scale * n_rays) / n_alive), nmax), min_samples);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        plan->n_alive = n_alive; plan->n_step = N;
+        plan[1].samples_done = done + N;
+    }
+    return make_int2(n_alive, N);
+}
+
 // One thread per alive ray, up to N_samples samples each (raymarching.cu:353-403 arithmetic,
 // including the calc_dt(..., cascades) quirk via p).  The marching loop only records t in LDS
 // (DS traffic does not sit in the vmcnt queue of the dependent bitfield loads); afterwards the
@@ -826,25 +867,16 @@ render_march_kernel(const float* __restrict__ rays_o, const float* __restrict__ 
     __shared__ float s_t[NMAX * 64];        // [sample][lane]; 16 KiB at NMAX = 64 allows two of these waves per SIMD, 8 KiB four
     __shared__ float s_ray[6 * 64];
     __shared__ int s_incl[64];
-    // rendering.py:65 `while samples < max_samples`: `samples` grows by N per iteration.  With a probe
-    // cap a ray can advance by fewer than N samples per iteration, so that mode budgets the samples
-    // per ray instead (emitted[r]); both bound a ray to max_samples (+ at most one chunk).
-    const int done = (probe_cap <= 0) ? plan->samples_done : 0;
-    const int n_alive = (done < max_samples_total) ? plan->n_alive_raw : 0;
-    int N = 0;
-    if (n_alive > 0) N = max(min((int)(((long long)chunk_scale * n_rays) / n_alive), NMAX), min_samples);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        plan->n_alive = n_alive; plan->n_step = N;
-        plan[1].samples_done = done + N;
-    }
+    const int2 step = render_plan_step(plan, n_rays, chunk_scale, min_samples, max_samples_total, NMAX, probe_cap <= 0);
+    const int n_alive = step.x, N = step.y;
     if (blockIdx.x * 64 >= n_alive) return;
     const int lane = threadIdx.x;
     const int n = blockIdx.x * 64 + lane;
     const bool active = n < n_alive;
 #ifdef NGP_RENDER_TIMING
     const unsigned long long clk0 = wall_clock64();
-    int n_probes = 0, n_short = 0, n_long = 0;           // hops of at most / more than 8 lattice steps (a cell's diagonal is 8 steps long)
 #endif
+    ProbeTally tally;
     // rays leaving the object walk the rest of the box cell by cell and emit nothing: a chain of dependent bitfield loads per lane,
     // as long as the longest walk in the wave.  With the 8^3-block bits in LDS the walk through empty blocks needs no global load.
     const uint32_t* any = nullptr;
@@ -865,28 +897,14 @@ render_march_kernel(const float* __restrict__ rays_o, const float* __restrict__ 
         // zero direction component has an infinite one and walks cell by cell
         const float hop_slack = 8.0f * (fabsf(t2) * 1.2e-7f + 1.2e-7f + 1.2e-7f * fmaxf(fabsf(ray.ix), fmaxf(fabsf(ray.iy), fabsf(ray.iz))));
         if (probe_cap <= 0) {
-            float t_resume = t;
-            int iters = 0;
-            while (t < t2 && s < N) {
-                if (++iters > MARCH_ITER_CAP) { atomicAdd(&g_march_guard[2], 1u); t_resume = t2; break; }
-#ifdef NGP_RENDER_TIMING
-                ++n_probes;
-#endif
-                float x, y, z, dt, t_next;
-                if (march_probe<SIMPLE>(ray, p, t, x, y, z, dt, t_next, nullptr, any, hop_slack)) {
-                    s_t[s * 64 + lane] = t;
-                    t += dt; ++s;
-                    t_resume = t;
-                } else {
-#ifdef NGP_RENDER_TIMING
-                    if (t_next - t > 8.5f * p.dt_lo) ++n_long; else ++n_short;
-#endif
-                    t = t_next;
-                }
-            }
+            float t_resume;
+            s = march_serial_walk<SIMPLE>(ray, p, t, t2, N, t_resume, [&](int k, float tk, float) { s_t[k * 64 + lane] = tk; },
+                                          any, hop_slack, &tally);
             if (s > 0) hits[2 * r] = t_resume;
             else flags = RENDER_RETIRE;                    // N_eff == 0 (volumerendering.cu:222)
         } else {
+            // the one other serial loop: it stops on a probe count that is no guard, resumes at the next untested lattice point and
+            // retires at the far hit -- three rules march_serial_walk would each need an argument for
             int probes = 0;
             for (;;) {
                 if (!(t < t2)) { flags = RENDER_RETIRE; break; }
@@ -934,13 +952,11 @@ render_march_kernel(const float* __restrict__ rays_o, const float* __restrict__ 
         const float t = s_t[k * 64 + lo];
         const float ox = s_ray[lo], oy = s_ray[64 + lo], oz = s_ray[128 + lo];
         const float dx = s_ray[192 + lo], dy = s_ray[256 + lo], dz = s_ray[320 + lo];
-        const size_t o = (size_t)base + j;
-        xyzs[3 * o] = fmaf(t, dx, ox); xyzs[3 * o + 1] = fmaf(t, dy, oy); xyzs[3 * o + 2] = fmaf(t, dz, oz);
-        dirs[3 * o] = dx; dirs[3 * o + 1] = dy; dirs[3 * o + 2] = dz;
-        ts[o] = t; deltas[o] = SIMPLE ? p.dt_lo : calc_dt(t, p);
+        write_sample(xyzs, dirs, deltas, ts, (size_t)base + j, ox, oy, oz, dx, dy, dz, t, SIMPLE ? p.dt_lo : calc_dt(t, p));
     }
 #ifdef NGP_RENDER_TIMING
     {
+        const int n_probes = tally.probes, n_short = tally.hops_short, n_long = tally.hops_long;
         int mx = n_probes, sm = n_probes;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { mx = max(mx, __shfl_xor(mx, o, 64)); sm += __shfl_xor(sm, o, 64); }
@@ -1041,9 +1057,7 @@ render_composite_kernel(const float* __restrict__ sigmas, const float* __restric
         keep = !retire;
     }
     const unsigned long long m = __ballot(keep);
-    int c = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    const int c = ngp_wave_sum_i32(cnt);
     if (lane == 0) { s_keep[wave] = __popcll(m); s_cnt[wave] = c; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1082,10 +1096,9 @@ render_finish_kernel(const float* __restrict__ opacity, float* __restrict__ rgb,
 
 // The same iteration with ONE WAVE PER RAY, for the late iterations of a frame: a few thousand rays x up to 64 samples each, where a
 // thread per ray is one long chain of dependent probes per lane (a launch over 64 rays took 20 us, one over 1 856 rays 51 us).  The
-// wave walks the ray's lattice a tile of 64 candidates at a time exactly as march_train_count_wave_kernel does (all candidates probed
-// at once with march_probe's arithmetic, skip chains closed by pointer doubling, the orbit of the entry lane on the scalar unit) and
-// stops after the ray's N-th sample like the serial loop: same samples, same resume point (t of the last sample + its step), same
-// N_eff / retire flags.  16 rays per workgroup: their counts are summed in LDS and the packed range is reserved with one atomic.
+// wave walks the ray's lattice with march_tile_walk into its LDS row and stops after the ray's N-th sample like the serial loop: same
+// samples, same resume point (t of the last sample + its step), same N_eff / retire flags.  16 rays per workgroup: their counts are
+// summed in LDS and the packed range is reserved with one atomic.
 // Reference chunking only (probe_cap == 0: the capped mode counts probes, which a tile does not have).
 constexpr int RENDER_WAVE_RAYS_PER_WG = 16;
 template <bool SIMPLE>
@@ -1098,14 +1111,8 @@ render_march_wave_kernel(const float* __restrict__ rays_o, const float* __restri
     __shared__ float s_t[RENDER_WAVE_RAYS_PER_WG][64];
     __shared__ int s_cnt[RENDER_WAVE_RAYS_PER_WG];
     __shared__ int s_base;
-    const int done = plan->samples_done;
-    const int n_alive = (done < max_samples_total) ? plan->n_alive_raw : 0;
-    int N = 0;
-    if (n_alive > 0) N = max(min((int)(((long long)chunk_scale * n_rays) / n_alive), 64), min_samples);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        plan->n_alive = n_alive; plan->n_step = N;
-        plan[1].samples_done = done + N;
-    }
+    const int2 step = render_plan_step(plan, n_rays, chunk_scale, min_samples, max_samples_total, 64, true);
+    const int n_alive = step.x, N = step.y;
     if ((int)blockIdx.x * RENDER_WAVE_RAYS_PER_WG >= n_alive) return;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -1117,86 +1124,7 @@ render_march_wave_kernel(const float* __restrict__ rays_o, const float* __restri
     if (active) {
         r = (size_t)alive[n];
         ray = load_ray(rays_o, rays_d, r);
-        const float t2 = hits[2 * r + 1];
-        float t_start = hits[2 * r];
-        float pending = -1.0f;                              // landing value of a skip that left the previous tile (< 0: none)
-        int tiles = 0;
-        for (;;) {
-            if (++tiles > MARCH_TILE_CAP) { if (lane == 0) atomicAdd(&g_march_guard[1], 1u); break; }
-            // 1. the tile's elements
-            float mine = t_start, t_end = t_start;
-            if (!(SIMPLE && lattice_tile_const_dt(t_start, p.dt_lo, lane, mine, t_end))) {
-                float tt = t_start;
-                mine = t_start;
-#pragma unroll 8
-                for (int j = 0; j < 64; ++j) {
-                    mine = (lane == j) ? tt : mine;
-                    tt += SIMPLE ? p.dt_lo : calc_dt(tt, p);
-                }
-                t_end = tt;
-            }
-            const int nvalid = __popcll(__ballot(mine < t2));                  // the sequence increases: valid lanes are a prefix
-            const int entry = pending >= 0 ? __popcll(__ballot(mine < pending)) : 0;
-            if (entry >= 64) {
-                if (nvalid < 64) break;
-                t_start = t_end;
-                continue;
-            }
-            // 2. all candidates at once
-            float x, y, z, dt, t_next = 0.f;
-            int k = 1;
-            const bool occ = march_probe<SIMPLE>(ray, p, mine, x, y, z, dt, t_next, &k);
-            const unsigned long long empty_mask = ~__ballot(occ);
-            // 3a. where does the chain of skips that starts at an empty lane end (pointer doubling, see march_train_count_wave_kernel)
-            int chain = occ ? ((lane << 8) | 64) : ((lane << 8) | (lane + k > 64 ? 64 : lane + k));
-#pragma unroll 1
-            for (int round = 0; round < 6; ++round) {
-                const int h = chain & 0xff;
-                const bool go = h < 64 && ((empty_mask >> h) & 1ull);
-                const int via = __builtin_amdgcn_ds_bpermute((h & 63) << 2, chain);
-                if (go) chain = via;
-                if (!__ballot(go)) break;
-            }
-            // 3b. the orbit of `entry`
-            unsigned long long emit = 0ull;
-            float next_pending = -1.0f;
-            bool finished = false;
-            int v = entry;
-            while (v < 64) {
-                if (v >= nvalid) { finished = true; break; }
-                if ((empty_mask >> v) & 1ull) {
-                    const int pk = __builtin_amdgcn_readlane(chain, v);
-                    const int h = pk & 0xff;
-                    if (h >= 64) {
-                        next_pending = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t_next), pk >> 8));
-                        v = 64;
-                        break;
-                    }
-                    v = h;
-                    continue;
-                }
-                const unsigned long long un = empty_mask >> v;
-                const int u = un ? v + (int)__builtin_ctzll(un) : 64;
-                const int hi = u < nvalid ? u : nvalid;
-                if (hi > v) {
-                    const int len = hi - v;
-                    emit |= (len >= 64 ? ~0ull : ((1ull << len) - 1ull)) << v;
-                }
-                if (nvalid < 64 && u >= nvalid) { finished = true; break; }
-                v = u;
-            }
-            // 4. the ray's next samples, N in all
-            const int room = N - s;
-            const bool my = (emit >> lane) & 1ull;
-            const int rank = __popcll(emit & ((1ull << lane) - 1ull));
-            if (my && rank < room) s_t[w][s + rank] = mine;
-            const int cnt = __popcll(emit);
-            s += cnt < room ? cnt : room;
-            if (finished || s >= N) break;
-            pending = next_pending;
-            if (pending >= 0 && !(pending < t2)) break;
-            t_start = t_end;
-        }
+        s = march_tile_walk<SIMPLE>(ray, p, hits[2 * r], hits[2 * r + 1], N, lane, (unsigned int)r, [&](int i, float t) { s_t[w][i] = t; });
         wave_lds_fence();
         if (s > 0) {
             const float t_last = s_t[w][s - 1];
@@ -1220,10 +1148,7 @@ render_march_wave_kernel(const float* __restrict__ rays_o, const float* __restri
     if (lane == 0) { offsets[n] = base; n_eff[n] = s | flags; }
     for (int j = lane; j < s; j += 64) {
         const float t = s_t[w][j];
-        const size_t o = (size_t)base + j;
-        xyzs[3 * o] = fmaf(t, ray.dx, ray.ox); xyzs[3 * o + 1] = fmaf(t, ray.dy, ray.oy); xyzs[3 * o + 2] = fmaf(t, ray.dz, ray.oz);
-        dirs[3 * o] = ray.dx; dirs[3 * o + 1] = ray.dy; dirs[3 * o + 2] = ray.dz;
-        ts[o] = t; deltas[o] = SIMPLE ? p.dt_lo : calc_dt(t, p);
+        write_sample(xyzs, dirs, deltas, ts, (size_t)base + j, ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, t, SIMPLE ? p.dt_lo : calc_dt(t, p));
     }
 }
 
@@ -1280,6 +1205,34 @@ static int g_render_wave_rays = 80000;              // ngp_debug_render_wave_ray
 double render_wait_limit_s() {
     static const double v = [] { const char* e = getenv("NGP_SPIN_TIMEOUT_S"); const double x = e ? atof(e) : 30.0; return x > 0 ? x : 30.0; }();
     return v;
+}
+
+// a run-time flag as a compile-time bool: f(std::true_type / std::false_type), so `decltype(S)::value` can be a kernel's template argument
+template <typename F> void with_bool(bool flag, F f) { if (flag) f(std::true_type{}); else f(std::false_type{}); }
+
+// Pass 1 of train marching, one WAVE per ray (march_train_count_wave_kernel: 64 candidates of the ray's fixed t-sequence probed per pass,
+// bit-identical to the serial loop, 101 us instead of 280-330 us per 8192-ray batch: profiles/archive_r01_r04/r01_v20_wave_march_kernel_trace.txt,
+// sweep of round 2: the step time is the same for every placement, the marching stream is busy a third as long).
+// pro != nullptr: the wave forms hits and jitter itself (hits_t, noise unused); else it reads them.
+void launch_train_count(const float* rays_o, const float* rays_d, const float* hits_t, const float* noise, const MarchParams& p, int max_samples,
+                        int n_rays, int64_t* rays_a, float* t_scratch, int32_t* counts, const MarchPrologue* pro, ngp_stream_t stream) {
+    const dim3 grid(ngp_div_up((long long)n_rays * 64, 256));
+    with_bool(p.simple, [&](auto S) { with_bool(pro != nullptr, [&](auto P) {
+        hipLaunchKernelGGL((march_train_count_wave_kernel<decltype(S)::value, decltype(P)::value>), grid, dim3(256), 0, ngp_stream(stream),
+                           rays_o, rays_d, hits_t, noise, p, max_samples, n_rays, rays_a, t_scratch, counts, pro ? *pro : MarchPrologue{});
+    }); });
+}
+
+// Pass 2 of train marching (march_train_write_kernel).  The expansion needs the step rule only: no bitfield, one cascade.
+// xyzs..ts may be null only when S == 0, which the kernel never dereferences.
+void launch_train_write(const float* rays_o, const float* rays_d, const int64_t* rays_a, const float* t_scratch, float scale, float exp_step_factor,
+                        int grid_size, int max_samples, int n_rays, float* xyzs, float* dirs, float* deltas, float* ts,
+                        int first_k, int32_t* list_k, int32_t* n_clear, const int32_t* offs_k,
+                        const int32_t* counts, int64_t* rays_a_out, int32_t* counter, ngp_stream_t stream) {
+    const MarchParams p = make_march_params(nullptr, 1, grid_size, scale, scale, exp_step_factor, max_samples);
+    hipLaunchKernelGGL(march_train_write_kernel, dim3(ngp_div_up((long long)n_rays * 64, 256)), dim3(256), 0, ngp_stream(stream),
+                       rays_o, rays_d, rays_a, t_scratch, p, max_samples, n_rays, xyzs, dirs, deltas, ts, first_k, list_k, n_clear, offs_k,
+                       counts, rays_a_out, counter);
 }
 
 }  // namespace
@@ -1430,16 +1383,7 @@ int ngp_raymarching_train_count_k(const float* rays_o, const float* rays_d, cons
         NGP_CHECK_PTR(rays_o); NGP_CHECK_PTR(rays_d); NGP_CHECK_PTR(hits_t); NGP_CHECK_PTR(density_bitfield);
         NGP_CHECK_PTR(noise); NGP_CHECK_PTR(rays_a); NGP_CHECK_PTR(t_scratch);
         const MarchParams p = make_march_params(density_bitfield, cascades, grid_size, scale, scale, exp_step_factor, max_samples);
-        // Pass 1 runs one WAVE per ray (march_train_count_wave_kernel: 64 candidates of the ray's fixed t-sequence probed per pass,
-        // bit-identical to the serial loop, 101 us instead of 280-330 us per 8192-ray batch: profiles/archive_r01_r04/r01_v20_wave_march_kernel_trace.txt,
-        // gpurun sweep of round 2: the step time is the same for every placement, the marching stream is busy a third as long).
-        const dim3 grid(ngp_div_up((long long)n_rays * 64, 256));
-        if (p.simple)
-            hipLaunchKernelGGL((march_train_count_wave_kernel<true, false>), grid, dim3(256), 0, ngp_stream(stream),
-                               rays_o, rays_d, hits_t, noise, p, max_samples, n_rays, rays_a, t_scratch, (int32_t*)nullptr, MarchPrologue{});
-        else
-            hipLaunchKernelGGL((march_train_count_wave_kernel<false, false>), grid, dim3(256), 0, ngp_stream(stream),
-                               rays_o, rays_d, hits_t, noise, p, max_samples, n_rays, rays_a, t_scratch, (int32_t*)nullptr, MarchPrologue{});
+        launch_train_count(rays_o, rays_d, hits_t, noise, p, max_samples, n_rays, rays_a, t_scratch, nullptr, nullptr, stream);
     }
     hipLaunchKernelGGL(march_train_scan_kernel, dim3(1), dim3(1024), 0, ngp_stream(stream), rays_a, n_rays, counter, first_k, offs_k);
     return NGP_LAUNCH_RESULT();
@@ -1452,11 +1396,8 @@ int ngp_raymarching_train_write(const float* rays_o, const float* rays_d, const 
     if (n_rays < 0 || grid_size < 1 || max_samples < 1) return NGP_EINVAL;
     if (n_rays == 0) return 0;
     NGP_CHECK_PTR(rays_o); NGP_CHECK_PTR(rays_d); NGP_CHECK_PTR(rays_a); NGP_CHECK_PTR(t_scratch);
-    // xyzs..ts may be null only when S == 0, which the kernel never dereferences
-    const MarchParams p = make_march_params(nullptr, 1, grid_size, scale, scale, exp_step_factor, max_samples);
-    hipLaunchKernelGGL(march_train_write_kernel, dim3(ngp_div_up((long long)n_rays * 64, 256)), dim3(256), 0, ngp_stream(stream),
-                       rays_o, rays_d, rays_a, t_scratch, p, max_samples, n_rays, xyzs, dirs, deltas, ts, 0, (int32_t*)nullptr,
-                       (int32_t*)nullptr, (const int32_t*)nullptr);
+    launch_train_write(rays_o, rays_d, rays_a, t_scratch, scale, exp_step_factor, grid_size, max_samples, n_rays, xyzs, dirs, deltas, ts,
+                       0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
     return NGP_LAUNCH_RESULT();
 }
 
@@ -1475,20 +1416,10 @@ int ngp_march_train_fused(const float* rays_o, const float* rays_d, const float*
     NGP_CHECK_PTR(xyzs); NGP_CHECK_PTR(dirs); NGP_CHECK_PTR(deltas); NGP_CHECK_PTR(ts);
     if (reinterpret_cast<uintptr_t>(counts) & 15) return NGP_EINVAL;               // (the prefix reads it 16 bytes at a time)
     const MarchParams p = make_march_params(density_bitfield, cascades, grid_size, scale, scale, exp_step_factor, max_samples);
-    MarchPrologue pro;
-    pro.center = center; pro.half_size = half_size; pro.near_distance = near_distance;
-    pro.seed_lo = (uint32_t)seed; pro.seed_hi = (uint32_t)(seed >> 32); pro.hits_out = hits_t; pro.noise_out = noise;
-    const dim3 grid(ngp_div_up((long long)n_rays * 64, 256));
-    if (p.simple)
-        hipLaunchKernelGGL((march_train_count_wave_kernel<true, true>), grid, dim3(256), 0, ngp_stream(stream),
-                           rays_o, rays_d, (const float*)nullptr, (const float*)nullptr, p, max_samples, n_rays, rays_a, t_scratch, counts, pro);
-    else
-        hipLaunchKernelGGL((march_train_count_wave_kernel<false, true>), grid, dim3(256), 0, ngp_stream(stream),
-                           rays_o, rays_d, (const float*)nullptr, (const float*)nullptr, p, max_samples, n_rays, rays_a, t_scratch, counts, pro);
-    const MarchParams pw = make_march_params(nullptr, 1, grid_size, scale, scale, exp_step_factor, max_samples);
-    hipLaunchKernelGGL(march_train_write_kernel, grid, dim3(256), 0, ngp_stream(stream),
-                       rays_o, rays_d, (const int64_t*)rays_a, (const float*)t_scratch, pw, max_samples, n_rays, xyzs, dirs, deltas, ts, 0, (int32_t*)nullptr,
-                       (int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)counts, rays_a, counter);
+    const MarchPrologue pro = {center, half_size, near_distance, (uint32_t)seed, (uint32_t)(seed >> 32), hits_t, noise};
+    launch_train_count(rays_o, rays_d, nullptr, nullptr, p, max_samples, n_rays, rays_a, t_scratch, counts, &pro, stream);
+    launch_train_write(rays_o, rays_d, rays_a, t_scratch, scale, exp_step_factor, grid_size, max_samples, n_rays, xyzs, dirs, deltas, ts,
+                       0, nullptr, nullptr, nullptr, counts, rays_a, counter, stream);
     return NGP_LAUNCH_RESULT();
 }
 
@@ -1500,10 +1431,8 @@ int ngp_raymarching_train_write_k(const float* rays_o, const float* rays_d, cons
     if (n_rays < 0 || grid_size < 1 || max_samples < 1 || first_k < 1 || first_k > 64) return NGP_EINVAL;
     if (n_rays == 0) return 0;
     NGP_CHECK_PTR(rays_o); NGP_CHECK_PTR(rays_d); NGP_CHECK_PTR(rays_a); NGP_CHECK_PTR(t_scratch); NGP_CHECK_PTR(list_k);
-    const MarchParams p = make_march_params(nullptr, 1, grid_size, scale, scale, exp_step_factor, max_samples);
-    hipLaunchKernelGGL(march_train_write_kernel, dim3(ngp_div_up((long long)n_rays * 64, 256)), dim3(256), 0, ngp_stream(stream),
-                       rays_o, rays_d, rays_a, t_scratch, p, max_samples, n_rays, xyzs, dirs, deltas, ts, first_k, list_k, n_clear,
-                       (const int32_t*)nullptr);
+    launch_train_write(rays_o, rays_d, rays_a, t_scratch, scale, exp_step_factor, grid_size, max_samples, n_rays, xyzs, dirs, deltas, ts,
+                       first_k, list_k, n_clear, nullptr, nullptr, nullptr, nullptr, stream);
     return NGP_LAUNCH_RESULT();
 }
 
@@ -1515,9 +1444,8 @@ int ngp_raymarching_train_write_kc(const float* rays_o, const float* rays_d, con
     if (n_rays < 0 || grid_size < 1 || max_samples < 1 || first_k < 1 || first_k > 64) return NGP_EINVAL;
     if (n_rays == 0) return 0;
     NGP_CHECK_PTR(rays_o); NGP_CHECK_PTR(rays_d); NGP_CHECK_PTR(rays_a); NGP_CHECK_PTR(t_scratch); NGP_CHECK_PTR(list_k); NGP_CHECK_PTR(offs_k);
-    const MarchParams p = make_march_params(nullptr, 1, grid_size, scale, scale, exp_step_factor, max_samples);
-    hipLaunchKernelGGL(march_train_write_kernel, dim3(ngp_div_up((long long)n_rays * 64, 256)), dim3(256), 0, ngp_stream(stream),
-                       rays_o, rays_d, rays_a, t_scratch, p, max_samples, n_rays, xyzs, dirs, deltas, ts, first_k, list_k, n_clear, offs_k);
+    launch_train_write(rays_o, rays_d, rays_a, t_scratch, scale, exp_step_factor, grid_size, max_samples, n_rays, xyzs, dirs, deltas, ts,
+                       first_k, list_k, n_clear, offs_k, nullptr, nullptr, nullptr, stream);
     return NGP_LAUNCH_RESULT();
 }
 
@@ -1535,12 +1463,10 @@ int ngp_raymarching_test(const float* rays_o, const float* rays_d, float* hits_t
     // the reference passes `cascades` where calc_dt expects `scale` (raymarching.cu:370,399)
     const MarchParams p = make_march_params(density_bitfield, cascades, grid_size, scale, (float)cascades, exp_step_factor, max_samples);
     // NB: the test kernel's dt clamp uses `cascades` as scale (reference quirk); with esf == 0 dt is dt_lo either way
-    if (p.simple)
-        hipLaunchKernelGGL(march_test_kernel<true>, dim3(ngp_div_up(n_alive, 64)), dim3(64), 0, ngp_stream(stream),
+    with_bool(p.simple, [&](auto S) {
+        hipLaunchKernelGGL(march_test_kernel<decltype(S)::value>, dim3(ngp_div_up(n_alive, 64)), dim3(64), 0, ngp_stream(stream),
                            rays_o, rays_d, hits_t, alive_indices, p, n_samples, n_alive, xyzs, dirs, deltas, ts, n_eff_samples);
-    else
-        hipLaunchKernelGGL(march_test_kernel<false>, dim3(ngp_div_up(n_alive, 64)), dim3(64), 0, ngp_stream(stream),
-                           rays_o, rays_d, hits_t, alive_indices, p, n_samples, n_alive, xyzs, dirs, deltas, ts, n_eff_samples);
+    });
     return NGP_LAUNCH_RESULT();
 }
 
@@ -1652,8 +1578,6 @@ int ngp_render_test_frame(const float* rays_o, const float* rays_d, const float*
         // the reference's chunking (chunk_scale 1, no probe cap) takes up to 64 samples per ray and iteration (rendering.py:72); the
         // regrouping modes cap a ray's samples per iteration at 32, which halves the marcher's LDS tile and doubles its waves per CU
         const bool regroup = chunk_scale > 1 || probe_cap > 0;
-#define NGP_RENDER_MARCH(S, NM) hipLaunchKernelGGL((render_march_kernel<S, NM>), mgrid, dim3(64), 0, st, rays_o, rays_d, hits, alive[it & 1], emitted, p, pl, \
-                                                   n_rays, chunk_scale, min_samples, max_samples, probe_cap, xyzs, dirs, deltas, ts, n_eff, offsets, block_any)
         // iteration 0 marches EVERY ray for N = max(chunk_scale, min_samples) samples (n_alive = n_rays): with a tile of 8 samples per
         // ray instead of 32 / 64 the longest walks of the frame run at the SIMDs' full wave count
         const bool first = it == 0 && chunk_scale <= 8;
@@ -1661,18 +1585,18 @@ int ngp_render_test_frame(const float* rays_o, const float* rays_d, const float*
         // two iterations ago, an upper bound of the rays alive now.  Crossover measured on the trained fields (tools/frame_wave_ab.py:
         // 0 / 16 384 / 80 000 / 200 000 rays -> 727 / 780 / 824 / 799 FPS on `lego`, 255 / 258 / 263 / 223 on `lego_hard`)
         const bool per_wave = !regroup && it >= LAG && bound <= (long long)g_render_wave_rays;
-        if (per_wave) {
-            const dim3 wgrid(ngp_div_up(bound, RENDER_WAVE_RAYS_PER_WG)), wblock(64 * RENDER_WAVE_RAYS_PER_WG);
-            if (p.simple) hipLaunchKernelGGL((render_march_wave_kernel<true>), wgrid, wblock, 0, st, rays_o, rays_d, hits, alive[it & 1], p, pl, n_rays, chunk_scale,
-                                             min_samples, max_samples, xyzs, dirs, deltas, ts, n_eff, offsets);
-            else hipLaunchKernelGGL((render_march_wave_kernel<false>), wgrid, wblock, 0, st, rays_o, rays_d, hits, alive[it & 1], p, pl, n_rays, chunk_scale,
-                                    min_samples, max_samples, xyzs, dirs, deltas, ts, n_eff, offsets);
-        } else if (p.simple) {
-            if (first) NGP_RENDER_MARCH(true, 8); else if (regroup) NGP_RENDER_MARCH(true, 32); else NGP_RENDER_MARCH(true, 64);
-        } else {
-            if (first) NGP_RENDER_MARCH(false, 8); else if (regroup) NGP_RENDER_MARCH(false, 32); else NGP_RENDER_MARCH(false, 64);
-        }
-#undef NGP_RENDER_MARCH
+        with_bool(p.simple, [&](auto S) {
+            auto serial = [&](auto NM) {               // NM: the LDS tile, samples per ray and iteration
+                hipLaunchKernelGGL((render_march_kernel<decltype(S)::value, decltype(NM)::value>), mgrid, dim3(64), 0, st, rays_o, rays_d, hits, alive[it & 1],
+                                   emitted, p, pl, n_rays, chunk_scale, min_samples, max_samples, probe_cap, xyzs, dirs, deltas, ts, n_eff, offsets, block_any);
+            };
+            if (per_wave)
+                hipLaunchKernelGGL((render_march_wave_kernel<decltype(S)::value>), dim3(ngp_div_up(bound, RENDER_WAVE_RAYS_PER_WG)), dim3(64 * RENDER_WAVE_RAYS_PER_WG),
+                                   0, st, rays_o, rays_d, hits, alive[it & 1], p, pl, n_rays, chunk_scale, min_samples, max_samples, xyzs, dirs, deltas, ts, n_eff, offsets);
+            else if (first) serial(std::integral_constant<int, 8>{});
+            else if (regroup) serial(std::integral_constant<int, 32>{});
+            else serial(std::integral_constant<int, 64>{});
+        });
         const int n_max = regroup ? 32 : 64;
         long long m_bound = (long long)chunk_scale * n_rays;
         if (n_max * bound < m_bound) m_bound = n_max * bound;
