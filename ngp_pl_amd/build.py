@@ -4,6 +4,8 @@
                      include/ngp_hip.h.  hipcc cross-compiles without a GPU.
   libngp_mesh.so  -- mesh export (marching cubes over a density volume) behind include/ngp_mesh.h; its sources
                      live under csrc/mesh/, apart from SOURCES.
+  libngp_meshfilter.so -- connected components and component filtering of a mesh behind include/ngp_meshfilter.h; its
+                     sources live under csrc/meshfilter/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -29,6 +31,9 @@ MESH_SOURCES = [os.path.join("mesh", "mesh.hip")]
 MESH_HEADERS = [os.path.join("mesh", "mc_tables.h"), os.path.join("..", "..", "include", "ngp_mesh.h")]
 # positions and normals are the plain f32 expressions of include/ngp_mesh.h (no fused multiply-add), as tests/mc_reference.py has them
 MESH_CFLAGS = ["-ffp-contract=off"]
+MESHFILTER_LIB = os.path.join(CSRC, "libngp_meshfilter.so")
+MESHFILTER_SOURCES = [os.path.join("meshfilter", "meshfilter.hip")]
+MESHFILTER_HEADERS = [os.path.join("..", "..", "include", "ngp_meshfilter.h")]
 
 
 def _stale(target, deps):
@@ -60,12 +65,14 @@ def _plan(sources, headers, extra, force):
 def build(force=False, verbose=False):
     objs, jobs = _plan(SOURCES, HEADERS, lambda src: EXTRA.get(src, []), force)
     mesh_objs, mesh_jobs = _plan(MESH_SOURCES, MESH_HEADERS, lambda src: MESH_CFLAGS, force)
-    if jobs or mesh_jobs:
+    filter_objs, filter_jobs = _plan(MESHFILTER_SOURCES, MESHFILTER_HEADERS, lambda src: [], force)
+    todo = jobs + mesh_jobs + filter_jobs
+    if todo:
         if verbose:
-            print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(jobs) + len(mesh_jobs), ARCH))
-        with ThreadPoolExecutor(max_workers=min(len(jobs) + len(mesh_jobs), os.cpu_count() or 1)) as ex:
-            list(ex.map(_run, jobs + mesh_jobs))
-    for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs)):
+            print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
+        with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 1)) as ex:
+            list(ex.map(_run, todo))
+    for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs), (MESHFILTER_LIB, filter_objs, filter_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

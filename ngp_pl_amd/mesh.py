@@ -3,9 +3,13 @@
     vol = density_volume(model, resolution=512)                    # (nz, ny, nx) f32 on the model's device
     m = marching_cubes(vol, threshold=20.0, bounds=(lo3, hi3))     # Mesh(vertices (V,3) f32, faces (F,3) i32, normals (V,3) f32)
     m = extract_mesh(model, resolution=512, threshold=20.0, colors=True)
+    c = connected_components(m)                                    # Components: labels = smallest vertex index, faces per component
+    m = filter_components(m, keep_largest=1)                       # drop the floaters (libngp_meshfilter.so); or min_faces=N
+    m = extract_mesh(model, 512, keep_largest=1, colors=True)      # the same, colours evaluated on the kept vertices only
     save_ply("mesh.ply", m)
 
-    python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] --out mesh.ply
+    python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
+                              [--min-component-faces N] --out mesh.ply
 
 Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
 [k, j, i]; vertices come back in world coordinates.  The reference's notebook (test.ipynb) instead samples
@@ -21,7 +25,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, _mesh_lib
+from . import _lib, _mesh_lib, _meshfilter_lib
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 
 INT32_MAX = 2 ** 31 - 1
@@ -147,15 +151,137 @@ def vertex_colors(model, vertices, normals, chunk=1 << 20):
     return out
 
 
-def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False):
-    """density_volume + marching_cubes in the model's world coordinates; colors=True adds vertex_colors."""
+@dataclasses.dataclass
+class Components:
+    vertex_label: object        # (V,) i32: the smallest vertex index of the vertex's component
+    face_label: object          # (F,) i32: the label of the face's first vertex
+    labels: object              # (C,) i32 ascending: the components with at least one face
+    faces_per_component: object  # (C,) i64
+    n_components: int           # C
+
+
+def _check_mesh(m):
+    """Shapes and dtypes (ValueError), then the device (the "no CPU path" RuntimeError); returns contiguous tensors."""
+    v, f = m.vertices, m.faces
+    if not isinstance(v, torch.Tensor) or v.dim() != 2 or v.shape[1] != 3 or v.dtype != torch.float32:
+        raise ValueError("mesh.vertices must be a (V, 3) float32 tensor")
+    if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[1] != 3 or f.dtype != torch.int32:
+        raise ValueError("mesh.faces must be a (F, 3) int32 tensor")
+    extra = []
+    for name in ("normals", "colors"):
+        a = getattr(m, name)
+        if a is not None and (not isinstance(a, torch.Tensor) or a.shape != v.shape or a.dtype != torch.float32):
+            raise ValueError("mesh.%s must be a (V, 3) float32 tensor or None" % name)
+        extra.append(a)
+    if v.shape[0] > INT32_MAX or f.shape[0] > INT32_MAX:
+        raise ValueError("more than INT32_MAX vertices or faces")
+    for name, a in (("vertices", v), ("faces", f), ("normals", extra[0]), ("colors", extra[1])):
+        if a is not None:
+            _require_cuda(a, "mesh." + name)
+            if a.device != v.device:
+                raise ValueError("mesh.%s is on %s, the vertices on %s" % (name, a.device, v.device))
+    return v.contiguous(), f.contiguous(), [None if a is None else a.contiguous() for a in extra]
+
+
+def _label(v, f):
+    """ngp_meshfilter_label -> Components; the table (labels, faces per component) is read off the per-vertex face counts, which
+    hold a component's count at its label's own index and 0 elsewhere."""
+    n_v, n_f, dev = v.shape[0], f.shape[0], v.device
+    vertex_label = torch.empty(n_v, dtype=torch.int32, device=dev)
+    face_label = torch.empty(n_f, dtype=torch.int32, device=dev)
+    component_faces = torch.empty(n_v, dtype=torch.int32, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if n_v or n_f:
+        with device_guard(dev):
+            _meshfilter_lib.call("ngp_meshfilter_label", ptr(f), n_v, n_f, ptr(vertex_label), ptr(face_label), ptr(component_faces),
+                                 ptr(count), stream())
+    labels = torch.nonzero(component_faces).view(-1)                  # ascending
+    return Components(vertex_label, face_label, labels.to(torch.int32), component_faces[labels].to(torch.int64), int(count.item()))
+
+
+def connected_components(mesh):
+    """Components of the mesh (two vertices are connected when a face holds both), labelled by their smallest vertex index: a
+    lock-free union-find over the faces on the GPU (include/ngp_meshfilter.h).  The result is the same on every run."""
+    v, f, _ = _check_mesh(mesh)
+    return _label(v, f)
+
+
+def _select(comps, keep_largest, min_faces):
+    """Bool (C,) over comps.labels: faces >= min_faces, and among the keep_largest components with the most faces (ties to the
+    smaller label); exact, on int64 keys."""
+    fpc, labels = comps.faces_per_component, comps.labels
+    sel = torch.ones(labels.shape[0], dtype=torch.bool, device=labels.device)
+    if min_faces is not None:
+        sel &= fpc >= int(min_faces)
+    if keep_largest is not None:
+        k = min(int(keep_largest), labels.shape[0])
+        key = (fpc << 32) | (INT32_MAX - labels.to(torch.int64))
+        top = torch.zeros_like(sel)
+        top[torch.topk(key, k).indices] = True
+        sel &= top
+    return sel
+
+
+def _filter(v, f, extra, comps, keep_largest, min_faces):
+    """The sub-mesh of the selected components and how many were selected: count, one host read of the totals, emit."""
+    if keep_largest is not None and int(keep_largest) < 0:
+        raise ValueError("keep_largest must be >= 0: %r" % (keep_largest,))
+    n_v, n_f, dev = v.shape[0], f.shape[0], v.device
+    sel = _select(comps, keep_largest, min_faces)
+    n_kept = int(sel.sum().item())
+    keep = torch.zeros(n_v, dtype=torch.uint8, device=dev)
+    keep[comps.labels[sel].to(torch.int64)] = 1
+    normals, colors = extra
+    n_ov = n_of = 0
+    if n_v or n_f:
+        ws_bytes = _meshfilter_lib.lib().ngp_meshfilter_workspace_bytes(n_v, n_f)
+        with device_guard(dev):
+            s = stream()
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            totals = torch.empty(2, dtype=torch.int64, device=dev)
+            _meshfilter_lib.call("ngp_meshfilter_count", ptr(f), ptr(comps.vertex_label), ptr(keep), n_v, n_f, ptr(ws), ws_bytes, ptr(totals), s)
+            n_ov, n_of = totals.tolist()
+    out = [torch.empty(n_ov, 3, dtype=torch.float32, device=dev) if a is not None else None for a in (v, normals, colors)]
+    faces = torch.empty(n_of, 3, dtype=torch.int32, device=dev)
+    if n_ov or n_of:
+        with device_guard(dev):
+            _meshfilter_lib.call("ngp_meshfilter_emit", ptr(f), ptr(comps.vertex_label), ptr(keep), ptr(v), ptr(normals), ptr(colors), n_v, n_f,
+                                 ptr(ws), ws_bytes, n_ov, n_of, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(faces), stream())
+    return Mesh(out[0], faces, out[1], out[2]), n_kept
+
+
+def filter_components(mesh, keep_largest=None, min_faces=None):
+    """The sub-mesh of the kept components: keep_largest=K keeps the K components with the most faces (ties to the smaller label),
+    min_faces=N those with at least N faces, both given both must hold; with neither the mesh itself is returned.  Kept vertices
+    (those a kept face references) and faces stay in their order, the faces re-indexed; positions, normals and colours are copied
+    bit for bit.  Nothing kept gives (0, 3) tensors.  One host sync for the selection, one for the output sizes."""
+    v, f, extra = _check_mesh(mesh)
+    if keep_largest is None and min_faces is None:
+        return mesh
+    return _filter(v, f, extra, _label(v, f), keep_largest, min_faces)[0]
+
+
+def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces):
+    """extract_mesh, and (components found, components kept) when a filter option is set (else None)."""
     lo, hi = _bounds(model, bounds)
     vol = density_volume(model, resolution, (lo, hi))
     m = marching_cubes(vol, threshold, (lo, hi))
     del vol
+    found = None
+    if keep_largest is not None or min_component_faces is not None:
+        v, f, extra = _check_mesh(m)
+        comps = _label(v, f)
+        m, kept = _filter(v, f, extra, comps, keep_largest, min_component_faces)
+        found = (comps.n_components, kept)
     if colors:
         m.colors = vertex_colors(model, m.vertices, m.normals)
-    return m
+    return m, found
+
+
+def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None):
+    """density_volume + marching_cubes in the model's world coordinates; keep_largest / min_component_faces filter the components
+    (filter_components); colors=True adds vertex_colors, evaluated after the filter on the kept vertices only."""
+    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces)[0]
 
 
 def _np(a):
@@ -200,18 +326,25 @@ def main(argv=None):
     ap.add_argument("--resolution", type=int, nargs="+", default=[512], help="N, or nx ny nz")
     ap.add_argument("--threshold", type=float, default=20.0, help="density iso-level (the notebook's sigma_threshold)")
     ap.add_argument("--colors", action="store_true", help="add vertex colours (the field seen along -normal)")
+    ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep the K connected components with the most faces")
+    ap.add_argument("--min-component-faces", type=int, default=None, metavar="N", help="drop connected components with fewer than N faces")
     ap.add_argument("--out", required=True, help="output .ply")
     a = ap.parse_args(argv)
     if len(a.resolution) not in (1, 3):
         ap.error("--resolution takes N or nx ny nz")
+    if a.keep_largest is not None and a.keep_largest < 0:
+        ap.error("--keep-largest takes K >= 0")
     from .networks import NGP
     from .utils import load_ckpt
     model = NGP(scale=a.scale, level_table=a.level_table).cuda()
     load_ckpt(model, a.ckpt, prefixes_to_ignore=("density_grid", "grid_coords"))
     res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
-    m = extract_mesh(model, res, a.threshold, colors=a.colors)
+    m, found = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces)
     save_ply(a.out, m)
-    print("%s: %d vertices, %d faces" % (a.out, m.vertices.shape[0], m.faces.shape[0]))
+    line = "%s: %d vertices, %d faces" % (a.out, m.vertices.shape[0], m.faces.shape[0])
+    if found is not None:
+        line += ", %d components found, %d kept" % found
+    print(line)
     return 0
 
 

@@ -1,9 +1,15 @@
 """Mesh export timing on the trained procedural scene: trains `--steps` native steps, then times extract_mesh at `--resolution`
 (wall time with a device sync, split into density volume and marching cubes; best of `--reps`) and prints one JSON line with V, F
 and the marching cubes' algorithmic bytes (volume read twice + outputs).  Under `rocprofv3 --kernel-trace --stats` the kernel
-times of the same extraction divide those bytes (rate / 8 TB/s = share of HBM peak)."""
+times of the same extraction divide those bytes (rate / 8 TB/s = share of HBM peak).
+
+The component filter is timed on that mesh: connected_components, then filter_components(keep_largest=1) (which labels again),
+each wall time with a device sync, best of `--reps`; V, F and the component count C before and after.  `--surface-stats N` adds, at
+resolution N, the component count, the largest component's share of the faces and the vertices' distance to the analytic surface
+(median / p95 in voxels) before and after keep_largest=1."""
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -28,12 +34,33 @@ def batch(n, seed, W=200):
     return ro, rd, gt.contiguous()
 
 
+def surface_error(m, n):
+    """|signed distance - iso distance| of the vertices, in voxels of an n^3 lattice over the unit box: median, p95."""
+    p = 20.0 / syn.SIGMA_INSIDE
+    sd_iso = -syn.EDGE * math.log(p / (1 - p))
+    d = (syn.signed_distance(m.vertices.double()) - sd_iso).abs() * (n - 1)
+    return d.median().item(), torch.quantile(d[torch.randperm(len(d), device=d.device)[:1000000]], 0.95).item()
+
+
+def best_of(reps, fn):
+    best, out = None, None
+    for _ in range(reps + 1):                         # the first round warms up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        best = dt if best is None or dt < best else best
+    return best, out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--resolution", type=int, default=512)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--threshold", type=float, default=20.0)
+    ap.add_argument("--surface-stats", type=int, default=0, metavar="N", help="also report the filter's effect on the N^3 mesh")
     a = ap.parse_args()
     torch.manual_seed(2)
     model = NGP(scale=0.5).cuda()
@@ -62,6 +89,21 @@ def main():
     V, F = m.vertices.shape[0], m.faces.shape[0]
     res.update(total_s=best[0], density_volume_s=best[1], marching_cubes_s=best[2], V=V, F=F,
                mc_algorithmic_bytes=2 * 4 * n ** 3 + V * 24 + F * 12)
+    t_label, comps = best_of(a.reps, lambda: mesh.connected_components(m))
+    t_filter, kept = best_of(a.reps, lambda: mesh.filter_components(m, keep_largest=1))
+    res.update(connected_components_s=t_label, filter_keep_largest_1_s=t_filter, C=comps.n_components,
+               V_kept=kept.vertices.shape[0], F_kept=kept.faces.shape[0], C_kept=mesh.connected_components(kept).n_components)
+    if a.surface_stats:
+        ns = a.surface_stats
+        ms = mesh.extract_mesh(model, ns, a.threshold)
+        cs = mesh.connected_components(ms)
+        mk = mesh.filter_components(ms, keep_largest=1)
+        before, after = surface_error(ms, ns), surface_error(mk, ns)
+        res.update(surface=dict(resolution=ns, V=ms.vertices.shape[0], F=ms.faces.shape[0], C=cs.n_components,
+                                largest_face_share=cs.faces_per_component.max().item() / ms.faces.shape[0],
+                                faces_per_component_top5=torch.sort(cs.faces_per_component, descending=True).values[:5].tolist(),
+                                V_kept=mk.vertices.shape[0], F_kept=mk.faces.shape[0],
+                                median_voxels=before[0], p95_voxels=before[1], median_voxels_kept=after[0], p95_voxels_kept=after[1]))
     print(json.dumps(res))
 
 
