@@ -6,6 +6,9 @@
                      live under csrc/mesh/, apart from SOURCES.
   libngp_meshfilter.so -- connected components and component filtering of a mesh behind include/ngp_meshfilter.h; its
                      sources live under csrc/meshfilter/.
+  libngp_meshcull.so -- depth-buffer visibility of a mesh against cameras and the cull of unseen faces behind
+                     include/ngp_meshcull.h; its sources live under csrc/meshcull/.  The order-preserving compaction
+                     (csrc/mesh_compact.h) is shared source of this library and the component filter.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -33,7 +36,12 @@ MESH_HEADERS = [os.path.join("mesh", "mc_tables.h"), os.path.join("..", "..", "i
 MESH_CFLAGS = ["-ffp-contract=off"]
 MESHFILTER_LIB = os.path.join(CSRC, "libngp_meshfilter.so")
 MESHFILTER_SOURCES = [os.path.join("meshfilter", "meshfilter.hip")]
-MESHFILTER_HEADERS = [os.path.join("..", "..", "include", "ngp_meshfilter.h")]
+MESHFILTER_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshfilter.h")]
+MESHCULL_LIB = os.path.join(CSRC, "libngp_meshcull.so")
+MESHCULL_SOURCES = [os.path.join("meshcull", "meshcull.hip")]
+MESHCULL_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshcull.h")]
+# projection, edge functions and depths are the plain f32 expressions of include/ngp_meshcull.h, as tests/mesh_visibility_reference.py has them
+MESHCULL_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -66,13 +74,15 @@ def build(force=False, verbose=False):
     objs, jobs = _plan(SOURCES, HEADERS, lambda src: EXTRA.get(src, []), force)
     mesh_objs, mesh_jobs = _plan(MESH_SOURCES, MESH_HEADERS, lambda src: MESH_CFLAGS, force)
     filter_objs, filter_jobs = _plan(MESHFILTER_SOURCES, MESHFILTER_HEADERS, lambda src: [], force)
-    todo = jobs + mesh_jobs + filter_jobs
+    cull_objs, cull_jobs = _plan(MESHCULL_SOURCES, MESHCULL_HEADERS, lambda src: MESHCULL_CFLAGS, force)
+    todo = jobs + mesh_jobs + filter_jobs + cull_jobs
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
         with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 1)) as ex:
             list(ex.map(_run, todo))
-    for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs), (MESHFILTER_LIB, filter_objs, filter_jobs)):
+    for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs), (MESHFILTER_LIB, filter_objs, filter_jobs),
+                            (MESHCULL_LIB, cull_objs, cull_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

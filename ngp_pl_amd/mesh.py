@@ -6,10 +6,13 @@
     c = connected_components(m)                                    # Components: labels = smallest vertex index, faces per component
     m = filter_components(m, keep_largest=1)                       # drop the floaters (libngp_meshfilter.so); or min_faces=N
     m = extract_mesh(model, 512, keep_largest=1, colors=True)      # the same, colours evaluated on the kept vertices only
+    n = vertex_views(m, K, poses, (W, H), bias=0.01)               # (V,) i32: in how many cameras each vertex is unoccluded
+    m = cull_invisible(m, K, poses, (W, H), bias=0.01)             # drop the faces no camera sees (libngp_meshcull.so)
+    m = extract_mesh(model, 512, keep_largest=1, cull=dict(K=K, poses=poses, img_wh=(W, H)))     # the same, after the filter
     save_ply("mesh.ply", m)
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
-                              [--min-component-faces N] --out mesh.ply
+                              [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]] --out mesh.ply
 
 Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
 [k, j, i]; vertices come back in world coordinates.  The reference's notebook (test.ipynb) instead samples
@@ -25,8 +28,9 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, _mesh_lib, _meshfilter_lib
+from . import _lib, _mesh_lib, _meshcull_lib, _meshfilter_lib
 from ._mesh_lib import bounds6, device_guard, ptr, stream
+from .networks import NEAR_DISTANCE
 
 INT32_MAX = 2 ** 31 - 1
 
@@ -261,8 +265,86 @@ def filter_components(mesh, keep_largest=None, min_faces=None):
     return _filter(v, f, extra, _label(v, f), keep_largest, min_faces)[0]
 
 
-def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces):
-    """extract_mesh, and (components found, components kept) when a filter option is set (else None)."""
+def _cameras(K, poses, img_wh, dev=None):
+    """K (3, 3), poses (C, 3 or 4, 4) and img_wh = (W, H) as NGP.mark_invisible_cells takes them -> f32 tensors on dev, W, H
+    (dev=None: the checks alone)."""
+    K, poses = torch.as_tensor(K), torch.as_tensor(poses)
+    if K.shape != (3, 3):
+        raise ValueError("K must be (3, 3): %r" % (tuple(K.shape),))
+    if poses.dim() != 3 or poses.shape[0] < 1 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
+        raise ValueError("poses must be (C, 3, 4) camera-to-world with C >= 1: %r" % (tuple(poses.shape),))
+    if len(img_wh) != 2 or not all(1 <= int(n) <= 16384 for n in img_wh):
+        raise ValueError("img_wh must be (W, H), each 1..16384: %r" % (img_wh,))
+    if dev is None:
+        return None
+    return (K.to(device=dev, dtype=torch.float32).contiguous(), poses[:, :3, :4].to(device=dev, dtype=torch.float32).contiguous(),
+            int(img_wh[0]), int(img_wh[1]))
+
+
+def _views(v, f, K, poses, img_wh, bias, near, max_zbuffer_bytes):
+    """ngp_meshcull_views -> vertex_views (V,) i32 and the depth workspace as (cameras per chunk, H, W) i32 bit patterns."""
+    n_v, n_f, dev = v.shape[0], f.shape[0], v.device
+    Kd, Pd, W, H = _cameras(K, poses, img_wh, dev)
+    n_cams = Pd.shape[0]
+    fit = max(1, min(n_cams, int(max_zbuffer_bytes) // (4 * W * H)))
+    views = torch.zeros(n_v, dtype=torch.int32, device=dev)
+    with device_guard(dev):
+        zbuf = torch.empty(fit, H, W, dtype=torch.int32, device=dev)
+        _meshcull_lib.call("ngp_meshcull_views", ptr(v), ptr(f), n_v, n_f, ptr(Kd), ptr(Pd), n_cams, W, H, float(near), float(bias),
+                           ptr(zbuf), zbuf.numel() * 4, ptr(views), stream())
+    return views, zbuf
+
+
+def vertex_views(mesh, K, poses, img_wh, bias, near=NEAR_DISTANCE, max_zbuffer_bytes=1 << 28, return_zbuffer=False):
+    """(V,) i32: the number of cameras in which each vertex has a view -- inside the image, at or beyond `near`, and not more than
+    `bias` (world units) behind the nearest surface of the mesh at its pixel (include/ngp_meshcull.h has the exact rule).  K (3, 3),
+    poses (C, 3, 4) camera-to-world and img_wh = (W, H) are NGP.mark_invisible_cells' arguments.  The mesh is rasterised into one
+    depth buffer per camera, as many cameras at a time as fit max_zbuffer_bytes (at least one); the result does not depend on that.
+    return_zbuffer=True also returns the depth workspace, (cameras per chunk, H, W) i32 holding the f32 depths' bits (+inf where no
+    face landed) of the last chunk.  No host sync."""
+    _cameras(K, poses, img_wh)
+    v, f, _ = _check_mesh(mesh)
+    views, zbuf = _views(v, f, K, poses, img_wh, bias, near, max_zbuffer_bytes)
+    return (views, zbuf) if return_zbuffer else views
+
+
+def _cull(v, f, extra, views, min_views):
+    """The sub-mesh of the faces with a vertex of at least min_views views: count, one host read of the totals, emit."""
+    n_v, n_f, dev = v.shape[0], f.shape[0], v.device
+    normals, colors = extra
+    n_ov = n_of = 0
+    if n_v or n_f:
+        ws_bytes = _meshcull_lib.lib().ngp_meshcull_workspace_bytes(n_v, n_f)
+        with device_guard(dev):
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            totals = torch.empty(2, dtype=torch.int64, device=dev)
+            _meshcull_lib.call("ngp_meshcull_count", ptr(f), ptr(views), int(min_views), n_v, n_f, ptr(ws), ws_bytes, ptr(totals), stream())
+            n_ov, n_of = totals.tolist()
+    out = [torch.empty(n_ov, 3, dtype=torch.float32, device=dev) if a is not None else None for a in (v, normals, colors)]
+    faces = torch.empty(n_of, 3, dtype=torch.int32, device=dev)
+    if n_ov or n_of:
+        with device_guard(dev):
+            _meshcull_lib.call("ngp_meshcull_emit", ptr(f), ptr(views), int(min_views), ptr(v), ptr(normals), ptr(colors), n_v, n_f, ptr(ws),
+                               ws_bytes, n_ov, n_of, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(faces), stream())
+    return Mesh(out[0], faces, out[1], out[2])
+
+
+def cull_invisible(mesh, K, poses, img_wh, bias, min_views=1, near=NEAR_DISTANCE, max_zbuffer_bytes=1 << 28):
+    """The sub-mesh of the faces some camera sees: a face is kept when at least one of its vertices has min_views views or more
+    (vertex_views); with min_views <= 0 the mesh itself is returned.  Kept vertices (those a kept face references) and faces stay in
+    their order, the faces re-indexed; positions, normals and colours are copied bit for bit.  Nothing kept gives (0, 3) tensors.
+    Mesh-only and geometric: the field is not read.  One host sync for the output sizes."""
+    _cameras(K, poses, img_wh)
+    v, f, extra = _check_mesh(mesh)
+    if int(min_views) <= 0:
+        return mesh
+    views, _ = _views(v, f, K, poses, img_wh, bias, near, max_zbuffer_bytes)
+    return _cull(v, f, extra, views, min_views)
+
+
+def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None):
+    """extract_mesh, (components found, components kept) when a filter option is set (else None), and the number of faces the cull
+    dropped when `cull` is set (else None)."""
     lo, hi = _bounds(model, bounds)
     vol = density_volume(model, resolution, (lo, hi))
     m = marching_cubes(vol, threshold, (lo, hi))
@@ -273,15 +355,26 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
         comps = _label(v, f)
         m, kept = _filter(v, f, extra, comps, keep_largest, min_component_faces)
         found = (comps.n_components, kept)
+    culled = None
+    if cull is not None:
+        opts = dict(cull)
+        bias = opts.pop("bias", None)
+        if bias is None:                                 # two voxels of the coarsest axis
+            bias = 2.0 * max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution)))
+        n_f = m.faces.shape[0]
+        m = cull_invisible(m, bias=bias, **opts)
+        culled = n_f - m.faces.shape[0]
     if colors:
         m.colors = vertex_colors(model, m.vertices, m.normals)
-    return m, found
+    return m, found, culled
 
 
-def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None):
+def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None, cull=None):
     """density_volume + marching_cubes in the model's world coordinates; keep_largest / min_component_faces filter the components
-    (filter_components); colors=True adds vertex_colors, evaluated after the filter on the kept vertices only."""
-    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces)[0]
+    (filter_components); cull=dict(K=, poses=, img_wh=, min_views=1, bias=None) then drops the faces none of those cameras sees
+    (cull_invisible; bias=None is twice the largest lattice spacing); colors=True adds vertex_colors, evaluated after both on the
+    kept vertices only."""
+    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull)[0]
 
 
 def _np(a):
@@ -328,6 +421,10 @@ def main(argv=None):
     ap.add_argument("--colors", action="store_true", help="add vertex colours (the field seen along -normal)")
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep the K connected components with the most faces")
     ap.add_argument("--min-component-faces", type=int, default=None, metavar="N", help="drop connected components with fewer than N faces")
+    ap.add_argument("--cull-cameras", default=None, metavar="FILE.npz",
+                    help="drop the faces none of these cameras sees: an .npz with K (3, 3), poses (C, 3, 4) camera-to-world and img_wh (W, H)")
+    ap.add_argument("--cull-min-views", type=int, default=1, metavar="N", help="views a vertex needs for its faces to be kept")
+    ap.add_argument("--cull-bias", type=float, default=None, metavar="B", help="depth slack in world units (default: two voxels)")
     ap.add_argument("--out", required=True, help="output .ply")
     a = ap.parse_args(argv)
     if len(a.resolution) not in (1, 3):
@@ -339,11 +436,18 @@ def main(argv=None):
     model = NGP(scale=a.scale, level_table=a.level_table).cuda()
     load_ckpt(model, a.ckpt, prefixes_to_ignore=("density_grid", "grid_coords"))
     res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
-    m, found = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces)
+    cull = None
+    if a.cull_cameras is not None:
+        with np.load(a.cull_cameras) as cams:
+            cull = dict(K=cams["K"], poses=cams["poses"], img_wh=tuple(int(n) for n in cams["img_wh"]), min_views=a.cull_min_views,
+                        bias=a.cull_bias)
+    m, found, culled = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull)
     save_ply(a.out, m)
     line = "%s: %d vertices, %d faces" % (a.out, m.vertices.shape[0], m.faces.shape[0])
     if found is not None:
         line += ", %d components found, %d kept" % found
+    if culled is not None:
+        line += ", %d faces culled as unseen" % culled
     print(line)
     return 0
 

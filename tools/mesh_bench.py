@@ -6,7 +6,12 @@ times of the same extraction divide those bytes (rate / 8 TB/s = share of HBM pe
 The component filter is timed on that mesh: connected_components, then filter_components(keep_largest=1) (which labels again),
 each wall time with a device sync, best of `--reps`; V, F and the component count C before and after.  `--surface-stats N` adds, at
 resolution N, the component count, the largest component's share of the faces and the vertices' distance to the analytic surface
-(median / p95 in voxels) before and after keep_largest=1."""
+(median / p95 in voxels) before and after keep_largest=1.
+
+The visibility cull is timed on the same mesh: cull_invisible against `--cull-cameras` synthetic.hemisphere_poses at
+`--cull-size`^2 pixels with a bias of two voxels, wall time with a device sync, best of `--reps`; V and F kept.  With
+`--surface-stats N` the vertex-to-surface median / p95 of the N^3 mesh after the cull for min_views = 1, 5, 25 and 50 of the cameras
+(vertices kept, median, p95 per row), and after keep_largest=1 followed by the cull."""
 import argparse
 import json
 import math
@@ -61,6 +66,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--threshold", type=float, default=20.0)
     ap.add_argument("--surface-stats", type=int, default=0, metavar="N", help="also report the filter's effect on the N^3 mesh")
+    ap.add_argument("--cull-cameras", type=int, default=100, metavar="C", help="cameras of the visibility cull")
+    ap.add_argument("--cull-size", type=int, default=800, metavar="W", help="image width and height of the visibility cull")
     a = ap.parse_args()
     torch.manual_seed(2)
     model = NGP(scale=0.5).cuda()
@@ -93,17 +100,29 @@ def main():
     t_filter, kept = best_of(a.reps, lambda: mesh.filter_components(m, keep_largest=1))
     res.update(connected_components_s=t_label, filter_keep_largest_1_s=t_filter, C=comps.n_components,
                V_kept=kept.vertices.shape[0], F_kept=kept.faces.shape[0], C_kept=mesh.connected_components(kept).n_components)
+    K, poses, wh = syn.intrinsics(a.cull_size), syn.hemisphere_poses(a.cull_cameras, seed=1), (a.cull_size, a.cull_size)
+    t_cull, seen = best_of(a.reps, lambda: mesh.cull_invisible(m, K, poses, wh, 2.0 / (n - 1)))
+    res.update(cull_invisible_s=t_cull, cull_cameras=a.cull_cameras, cull_size=a.cull_size, V_seen=seen.vertices.shape[0], F_seen=seen.faces.shape[0])
     if a.surface_stats:
         ns = a.surface_stats
         ms = mesh.extract_mesh(model, ns, a.threshold)
         cs = mesh.connected_components(ms)
         mk = mesh.filter_components(ms, keep_largest=1)
         before, after = surface_error(ms, ns), surface_error(mk, ns)
+        mc, mkc = [mesh.cull_invisible(x, K, poses, wh, 2.0 / (ns - 1)) for x in (ms, mk)]
+        culled, both = surface_error(mc, ns), surface_error(mkc, ns)
+        by_min_views = {}
+        for mv in (1, 5, 25, 50):
+            x = mesh.cull_invisible(ms, K, poses, wh, 2.0 / (ns - 1), min_views=mv)
+            by_min_views[mv] = (x.vertices.shape[0],) + (surface_error(x, ns) if x.vertices.shape[0] else (None, None))
         res.update(surface=dict(resolution=ns, V=ms.vertices.shape[0], F=ms.faces.shape[0], C=cs.n_components,
                                 largest_face_share=cs.faces_per_component.max().item() / ms.faces.shape[0],
                                 faces_per_component_top5=torch.sort(cs.faces_per_component, descending=True).values[:5].tolist(),
                                 V_kept=mk.vertices.shape[0], F_kept=mk.faces.shape[0],
-                                median_voxels=before[0], p95_voxels=before[1], median_voxels_kept=after[0], p95_voxels_kept=after[1]))
+                                median_voxels=before[0], p95_voxels=before[1], median_voxels_kept=after[0], p95_voxels_kept=after[1],
+                                V_seen=mc.vertices.shape[0], F_seen=mc.faces.shape[0], median_voxels_seen=culled[0], p95_voxels_seen=culled[1],
+                                V_kept_seen=mkc.vertices.shape[0], F_kept_seen=mkc.faces.shape[0], median_voxels_kept_seen=both[0],
+                                p95_voxels_kept_seen=both[1], seen_by_min_views=by_min_views))
     print(json.dumps(res))
 
 
