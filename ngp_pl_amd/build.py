@@ -8,7 +8,9 @@
                      sources live under csrc/meshfilter/.
   libngp_meshcull.so -- depth-buffer visibility of a mesh against cameras and the cull of unseen faces behind
                      include/ngp_meshcull.h; its sources live under csrc/meshcull/.  The order-preserving compaction
-                     (csrc/mesh_compact.h) is shared source of this library and the component filter.
+                     (csrc/mesh_compact.h) is shared source of this library, the component filter and the simplifier.
+  libngp_meshsimplify.so -- simplification of a mesh by vertex clustering behind include/ngp_meshsimplify.h; its sources
+                     live under csrc/meshsimplify/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -42,6 +44,11 @@ MESHCULL_SOURCES = [os.path.join("meshcull", "meshcull.hip")]
 MESHCULL_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshcull.h")]
 # projection, edge functions and depths are the plain f32 expressions of include/ngp_meshcull.h, as tests/mesh_visibility_reference.py has them
 MESHCULL_CFLAGS = ["-ffp-contract=off"]
+MESHSIMPLIFY_LIB = os.path.join(CSRC, "libngp_meshsimplify.so")
+MESHSIMPLIFY_SOURCES = [os.path.join("meshsimplify", "meshsimplify.hip")]
+MESHSIMPLIFY_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshsimplify.h")]
+# cells, fixed-point fractions and the f64 means are the plain expressions of include/ngp_meshsimplify.h, as tests/mesh_simplify_reference.py has them
+MESHSIMPLIFY_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -75,14 +82,15 @@ def build(force=False, verbose=False):
     mesh_objs, mesh_jobs = _plan(MESH_SOURCES, MESH_HEADERS, lambda src: MESH_CFLAGS, force)
     filter_objs, filter_jobs = _plan(MESHFILTER_SOURCES, MESHFILTER_HEADERS, lambda src: [], force)
     cull_objs, cull_jobs = _plan(MESHCULL_SOURCES, MESHCULL_HEADERS, lambda src: MESHCULL_CFLAGS, force)
-    todo = jobs + mesh_jobs + filter_jobs + cull_jobs
+    simplify_objs, simplify_jobs = _plan(MESHSIMPLIFY_SOURCES, MESHSIMPLIFY_HEADERS, lambda src: MESHSIMPLIFY_CFLAGS, force)
+    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
         with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 1)) as ex:
             list(ex.map(_run, todo))
     for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs), (MESHFILTER_LIB, filter_objs, filter_jobs),
-                            (MESHCULL_LIB, cull_objs, cull_jobs)):
+                            (MESHCULL_LIB, cull_objs, cull_jobs), (MESHSIMPLIFY_LIB, simplify_objs, simplify_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

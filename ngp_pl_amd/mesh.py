@@ -9,10 +9,14 @@
     n = vertex_views(m, K, poses, (W, H), bias=0.01)               # (V,) i32: in how many cameras each vertex is unoccluded
     m = cull_invisible(m, K, poses, (W, H), bias=0.01)             # drop the faces no camera sees (libngp_meshcull.so)
     m = extract_mesh(model, 512, keep_largest=1, cull=dict(K=K, poses=poses, img_wh=(W, H)))     # the same, after the filter
+    l = vertex_clusters(m, cell=0.004)                             # (V,) i32: smallest vertex index in the vertex's grid cell
+    m = simplify_clusters(m, cell=0.004)                           # one vertex per occupied cell (libngp_meshsimplify.so)
+    m = extract_mesh(model, 512, keep_largest=1, simplify_voxels=2, colors=True)     # cells of 2 voxels, after filter and cull
     save_ply("mesh.ply", m)
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
-                              [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]] --out mesh.ply
+                              [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]]
+                              [--simplify-voxels K] --out mesh.ply
 
 Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
 [k, j, i]; vertices come back in world coordinates.  The reference's notebook (test.ipynb) instead samples
@@ -23,12 +27,13 @@ sigma_threshold.  The occupancy grid is not used: every lattice point is evaluat
 import argparse
 import ctypes as C
 import dataclasses
+import math
 import sys
 
 import numpy as np
 import torch
 
-from . import _lib, _mesh_lib, _meshcull_lib, _meshfilter_lib
+from . import _lib, _mesh_lib, _meshcull_lib, _meshfilter_lib, _meshsimplify_lib
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -342,9 +347,93 @@ def cull_invisible(mesh, K, poses, img_wh, bias, min_views=1, near=NEAR_DISTANCE
     return _cull(v, f, extra, views, min_views)
 
 
-def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None):
-    """extract_mesh, (components found, components kept) when a filter option is set (else None), and the number of faces the cull
-    dropped when `cull` is set (else None)."""
+def _grid(cell, origin):
+    """cell as a float that is finite and > 0, origin as None or 3 floats (ValueError otherwise)."""
+    try:
+        cell = float(cell)
+    except (TypeError, ValueError):
+        raise ValueError("cell must be a number: %r" % (cell,))
+    if not (math.isfinite(cell) and cell > 0 and math.isfinite(C.c_float(cell).value) and C.c_float(cell).value > 0):
+        raise ValueError("cell must be finite and > 0 (as a float32): %r" % (cell,))
+    if origin is not None:
+        if isinstance(origin, torch.Tensor):
+            if origin.numel() != 3:
+                raise ValueError("origin must be 3 floats: shape %r" % (tuple(origin.shape),))
+        else:
+            origin = [float(x) for x in np.asarray(origin, np.float64).reshape(-1)]
+            if len(origin) != 3:
+                raise ValueError("origin must be 3 floats: %r" % (origin,))
+    return cell, origin
+
+
+def _cluster(v, extra, cell, origin, n_f):
+    """ngp_meshsimplify_cluster -> vertex_label (V,) i32, the workspace (sized for n_f faces) and the origin on the device."""
+    n_v, dev = v.shape[0], v.device
+    if origin is None:
+        o = v.amin(0)                                    # on the device: no sync
+    else:
+        o = torch.as_tensor(origin, dtype=torch.float32).reshape(3).to(dev)
+    o = o.contiguous()
+    label = torch.empty(n_v, dtype=torch.int32, device=dev)
+    ws_bytes = _meshsimplify_lib.lib().ngp_meshsimplify_workspace_bytes(n_v, n_f)
+    with device_guard(dev):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _meshsimplify_lib.call("ngp_meshsimplify_cluster", ptr(v), ptr(extra[0]), ptr(extra[1]), n_v, ptr(o), cell, ptr(ws), ws_bytes,
+                               ptr(label), stream())
+    return label, ws, ws_bytes, o
+
+
+def vertex_clusters(mesh, cell, origin=None):
+    """(V,) i32: the smallest vertex index among the vertices in the same cell of the uniform grid of edge `cell` that starts at
+    `origin` (3 floats; None: the vertices' minimum per axis, taken on the device), -1 for a vertex outside the grid (a coordinate
+    that is not finite, below the origin or 2^21 cells or more beyond it).  include/ngp_meshsimplify.h has the exact rule.
+    No host sync."""
+    cell, origin = _grid(cell, origin)
+    v, f, _ = _check_mesh(mesh)
+    if v.shape[0] == 0:
+        return torch.empty(0, dtype=torch.int32, device=v.device)
+    return _cluster(v, (None, None), cell, origin, 0)[0]
+
+
+def _simplify(v, f, extra, cell, origin):
+    """cluster, count, one host read of the totals, emit -> the simplified Mesh, vertex_label (V,) i32 and the totals
+    (output vertices, output faces, clusters)."""
+    n_v, n_f, dev = v.shape[0], f.shape[0], v.device
+    normals, colors = extra
+    n_ov = n_of = n_clusters = 0
+    label = torch.empty(0, dtype=torch.int32, device=dev)
+    if n_v:
+        label, ws, ws_bytes, o = _cluster(v, extra, cell, origin, n_f)
+        with device_guard(dev):
+            totals = torch.empty(3, dtype=torch.int64, device=dev)
+            _meshsimplify_lib.call("ngp_meshsimplify_count", ptr(f), ptr(label), n_v, n_f, ptr(ws), ws_bytes, ptr(totals), stream())
+            n_ov, n_of, n_clusters = totals.tolist()
+    out = [torch.empty(n_ov, 3, dtype=torch.float32, device=dev) if a is not None else None for a in (v, normals, colors)]
+    faces = torch.empty(n_of, 3, dtype=torch.int32, device=dev)
+    if n_ov or n_of:
+        with device_guard(dev):
+            _meshsimplify_lib.call("ngp_meshsimplify_emit", ptr(v), n_v, n_f, ptr(o), cell, ptr(ws), ws_bytes, n_ov, n_of, ptr(out[0]),
+                                   ptr(out[1]), ptr(out[2]), ptr(faces), stream())
+    return Mesh(out[0], faces, out[1], out[2]), label, (n_ov, n_of, n_clusters)
+
+
+def simplify_clusters(mesh, cell, origin=None):
+    """The mesh with every cluster of vertex_clusters merged into one vertex: its position is the mean of the members' positions,
+    its normal the normalised sum of theirs, its colour their mean (None stays None), each summed exactly in 2^-20 fixed point so
+    that the result is the same on every run.  Faces that lose a corner to a merge go, and of the faces that end on the same three
+    clusters the first stays, in its own orientation; vertices come back in the order of their clusters' smallest members, faces in
+    their own order.  Nothing kept gives (0, 3) tensors.  Clustering can pinch a thin wall: the result need not be manifold.
+    Mesh-only: the field is not read.  One host sync for the output sizes."""
+    cell, origin = _grid(cell, origin)
+    v, f, extra = _check_mesh(mesh)
+    return _simplify(v, f, extra, cell, origin)[0]
+
+
+def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None, simplify_voxels=None):
+    """extract_mesh, (components found, components kept) when a filter option is set (else None), the number of faces the cull
+    dropped when `cull` is set (else None), and (V0, V1, F0, F1) around the simplification when simplify_voxels is set (else None)."""
+    if simplify_voxels is not None and not (math.isfinite(float(simplify_voxels)) and float(simplify_voxels) > 0):
+        raise ValueError("simplify_voxels must be a finite number > 0: %r" % (simplify_voxels,))
     lo, hi = _bounds(model, bounds)
     vol = density_volume(model, resolution, (lo, hi))
     m = marching_cubes(vol, threshold, (lo, hi))
@@ -364,17 +453,25 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
         n_f = m.faces.shape[0]
         m = cull_invisible(m, bias=bias, **opts)
         culled = n_f - m.faces.shape[0]
+    simplified = None
+    if simplify_voxels is not None:
+        cell = float(simplify_voxels) * max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution)))
+        before = (m.vertices.shape[0], m.faces.shape[0])
+        m = simplify_clusters(m, cell, origin=lo)
+        simplified = (before[0], m.vertices.shape[0], before[1], m.faces.shape[0])
     if colors:
         m.colors = vertex_colors(model, m.vertices, m.normals)
-    return m, found, culled
+    return m, found, culled, simplified
 
 
-def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None, cull=None):
+def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None, cull=None,
+                 simplify_voxels=None):
     """density_volume + marching_cubes in the model's world coordinates; keep_largest / min_component_faces filter the components
     (filter_components); cull=dict(K=, poses=, img_wh=, min_views=1, bias=None) then drops the faces none of those cameras sees
-    (cull_invisible; bias=None is twice the largest lattice spacing); colors=True adds vertex_colors, evaluated after both on the
-    kept vertices only."""
-    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull)[0]
+    (cull_invisible; bias=None is twice the largest lattice spacing); simplify_voxels=K then merges the vertices of every grid
+    cell of K times the largest lattice spacing, the grid starting at the bounds' lower corner (simplify_clusters); colors=True adds
+    vertex_colors, evaluated after all three on the vertices that are left, along minus their (averaged) normals."""
+    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels)[0]
 
 
 def _np(a):
@@ -425,12 +522,16 @@ def main(argv=None):
                     help="drop the faces none of these cameras sees: an .npz with K (3, 3), poses (C, 3, 4) camera-to-world and img_wh (W, H)")
     ap.add_argument("--cull-min-views", type=int, default=1, metavar="N", help="views a vertex needs for its faces to be kept")
     ap.add_argument("--cull-bias", type=float, default=None, metavar="B", help="depth slack in world units (default: two voxels)")
+    ap.add_argument("--simplify-voxels", type=float, default=None, metavar="K",
+                    help="merge the vertices of every grid cell of K voxels (vertex clustering), after the filter and the cull")
     ap.add_argument("--out", required=True, help="output .ply")
     a = ap.parse_args(argv)
     if len(a.resolution) not in (1, 3):
         ap.error("--resolution takes N or nx ny nz")
     if a.keep_largest is not None and a.keep_largest < 0:
         ap.error("--keep-largest takes K >= 0")
+    if a.simplify_voxels is not None and not (math.isfinite(a.simplify_voxels) and a.simplify_voxels > 0):
+        ap.error("--simplify-voxels takes K > 0")
     from .networks import NGP
     from .utils import load_ckpt
     model = NGP(scale=a.scale, level_table=a.level_table).cuda()
@@ -441,13 +542,15 @@ def main(argv=None):
         with np.load(a.cull_cameras) as cams:
             cull = dict(K=cams["K"], poses=cams["poses"], img_wh=tuple(int(n) for n in cams["img_wh"]), min_views=a.cull_min_views,
                         bias=a.cull_bias)
-    m, found, culled = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull)
+    m, found, culled, simplified = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull, a.simplify_voxels)
     save_ply(a.out, m)
     line = "%s: %d vertices, %d faces" % (a.out, m.vertices.shape[0], m.faces.shape[0])
     if found is not None:
         line += ", %d components found, %d kept" % found
     if culled is not None:
         line += ", %d faces culled as unseen" % culled
+    if simplified is not None:
+        line += ", simplified %d -> %d vertices, %d -> %d faces" % simplified
     print(line)
     return 0
 

@@ -11,7 +11,11 @@ resolution N, the component count, the largest component's share of the faces an
 The visibility cull is timed on the same mesh: cull_invisible against `--cull-cameras` synthetic.hemisphere_poses at
 `--cull-size`^2 pixels with a bias of two voxels, wall time with a device sync, best of `--reps`; V and F kept.  With
 `--surface-stats N` the vertex-to-surface median / p95 of the N^3 mesh after the cull for min_views = 1, 5, 25 and 50 of the cameras
-(vertices kept, median, p95 per row), and after keep_largest=1 followed by the cull."""
+(vertices kept, median, p95 per row), and after keep_largest=1 followed by the cull.
+
+The simplification is timed on the same mesh: simplify_clusters with cells of K = 2 and K = 4 voxels from the box's lower corner
+(as extract_mesh(simplify_voxels=K) calls it), wall time with a device sync, best of `--reps`; V and F before and after.  With
+`--surface-stats N` the vertex-to-surface median / p95 of the N^3 mesh after each."""
 import argparse
 import json
 import math
@@ -103,6 +107,9 @@ def main():
     K, poses, wh = syn.intrinsics(a.cull_size), syn.hemisphere_poses(a.cull_cameras, seed=1), (a.cull_size, a.cull_size)
     t_cull, seen = best_of(a.reps, lambda: mesh.cull_invisible(m, K, poses, wh, 2.0 / (n - 1)))
     res.update(cull_invisible_s=t_cull, cull_cameras=a.cull_cameras, cull_size=a.cull_size, V_seen=seen.vertices.shape[0], F_seen=seen.faces.shape[0])
+    for k in (2, 4):
+        t_simplify, small = best_of(a.reps, lambda: mesh.simplify_clusters(m, k * max((h - l) / (n - 1) for l, h in zip(lo, hi)), origin=lo))
+        res.update({"simplify_k%d_s" % k: t_simplify, "V_simplified_k%d" % k: small.vertices.shape[0], "F_simplified_k%d" % k: small.faces.shape[0]})
     if a.surface_stats:
         ns = a.surface_stats
         ms = mesh.extract_mesh(model, ns, a.threshold)
@@ -115,7 +122,11 @@ def main():
         for mv in (1, 5, 25, 50):
             x = mesh.cull_invisible(ms, K, poses, wh, 2.0 / (ns - 1), min_views=mv)
             by_min_views[mv] = (x.vertices.shape[0],) + (surface_error(x, ns) if x.vertices.shape[0] else (None, None))
-        res.update(surface=dict(resolution=ns, V=ms.vertices.shape[0], F=ms.faces.shape[0], C=cs.n_components,
+        simplified = {}
+        for k in (2, 4):
+            x = mesh.simplify_clusters(ms, k * max((h - l) / (ns - 1) for l, h in zip(lo, hi)), origin=lo)
+            simplified[k] = (x.vertices.shape[0], x.faces.shape[0]) + (surface_error(x, ns) if x.vertices.shape[0] else (None, None))
+        res.update(surface=dict(resolution=ns, simplified_by_voxels=simplified, V=ms.vertices.shape[0], F=ms.faces.shape[0], C=cs.n_components,
                                 largest_face_share=cs.faces_per_component.max().item() / ms.faces.shape[0],
                                 faces_per_component_top5=torch.sort(cs.faces_per_component, descending=True).values[:5].tolist(),
                                 V_kept=mk.vertices.shape[0], F_kept=mk.faces.shape[0],
