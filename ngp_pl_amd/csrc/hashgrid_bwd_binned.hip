@@ -22,6 +22,11 @@
 //     expensive (dense) ones first.
 // Levels with few slices (the coarse dense ones: a z-slab can hold most of the scene) additionally split
 // their lists over K tasks whose partial tables are summed by a small merge kernel (no atomics anywhere).
+// What is exact and what is not: on every level with ONE task per slice (all hashed levels) an entry is
+// f16(clamp(f32(Q) * 2^-24)) of its exact integer sum Q -- bit for bit whatever the order.  On the K-split (dense)
+// levels each of the K <= 16 tasks rounds ITS integer sum to f32 and merge_kernel adds the K partials in f32, in
+// part order: deterministic, but up to 2 K roundings of 2^-24 of the entry's mass away from the exact sum
+// (tests/test_table_backward_exact_gpu.py holds both statements against tests/table_backward_reference.py).
 #include "hashgrid_common.h"
 #include <hip/hip_fp16.h>
 

@@ -79,9 +79,11 @@ def _corner_indices(meta, l, pg):
     return out
 
 
-def hash_encode(x01, table, meta, quantize=False):
+def hash_encode(x01, table, meta, quantize=False, value_dtype=torch.float32):
     """kernel_grid of grid.h.  x01 (S,3) f32 in [0,1]; table (total, F) float tensor (may require
-    grad).  Returns (S, L*F) f32, feature index l*F + f."""
+    grad).  Returns (S, L*F) f32, feature index l*F + f.  value_dtype=torch.float64: positions and
+    corner weights stay f32 as above, the weight x value products and their sums (forward and
+    autograd) are taken in f64."""
     x01 = x01.float()
     feats = []
     for l in range(meta.n_levels):
@@ -96,8 +98,8 @@ def hash_encode(x01, table, meta, quantize=False):
             wx = w[:, 0] if (c & 1) else 1 - w[:, 0]
             wy = w[:, 1] if ((c >> 1) & 1) else 1 - w[:, 1]
             wz = w[:, 2] if (c >> 2) else 1 - w[:, 2]
-            val = table[meta.offset[l] + idxs[c]].float()
-            acc = acc + (wx * wy * wz)[:, None] * val
+            val = table[meta.offset[l] + idxs[c]].to(value_dtype)
+            acc = acc + (wx * wy * wz).to(value_dtype)[:, None] * val
         feats.append(acc)
     out = torch.cat(feats, 1)
     return q16(out) if quantize else out

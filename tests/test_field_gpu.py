@@ -136,6 +136,49 @@ def test_hashgrid_backward(lib, field, mode):
     err = (got - want).abs().max().item() / scale
     assert err < tol, "max error %g of max |grad| %g" % (err, scale)
     assert (got != 0).sum() == (want != 0).sum() or mode != "atomic_f32"
+    # ---- per entry, against the exact integer sums Q * 2^-24 of tests/table_backward_reference.py -------------------------------------
+    # n_e contributions p_i = f32(w * g) reach an entry; the reference holds q_i = rint(p_i * 2^24), so |p_i - q_i 2^-24| <= 2^-25 and
+    # sum |p_i| <= M+ = M_e + n_e 2^-25.  A sum of n terms with one rounding of relative size u per operation is off by at most
+    # gamma(k) * sum |p_i|, gamma(k) = k u / (1 - k u), k the number of roundings a term can pass through:
+    #   atomic_f32: f32 atomics into an f32 table, no f16 store.  u = 2^-24, k = n_e - 1 (the add to the zeroed entry is exact).
+    #   atomic_f16: every p_i is converted to f16 (u = 2^-11; below the normal range the conversion is off by up to 2^-25 instead) and
+    #               every packed-f16 atomic rounds its sum: k = n_e.
+    #   sliced:     hashed levels as atomic_f16, in LDS.  Dense levels: up to 16 consecutive samples are summed in f32 registers by
+    #               fmaf (17 roundings of 2^-24), the run's sum is converted to f16 and added in LDS, and the K <= 4 private copies
+    #               are merged by f16 atomics: k <= n_e + 4, plus 17 * 2^-24 M+.
+    #   binned:     exact on the hashed levels: equality.  (tests/test_table_backward_exact_gpu.py holds the dense levels.)
+    # Every derived bound carries n_e 2^-25 for the reference's own quantisation.  The assertion is the smaller of the derived bound
+    # and the present one (tol * max |grad|), per entry: an entry with a single contribution is held to one rounding.
+    from tests import table_backward_cases as K
+    from tests import table_backward_reference as R
+    grid = K.grid_arrays(meta, "product")
+    ref = R.table_backward_reference(x.numpy(), grid.xyz_min, grid.xyz_max, dfl.cpu().numpy(), grid.resolution, grid.offset, grid.scale, keep_terms=False)
+    exact = ref.Q.astype(np.float64) / R.FIX_ONE
+    n_e = ref.n_e[:, None].astype(np.float64)
+    m_plus = ref.M_e + n_e * 2.0 ** -25
+
+    def gamma(k, u):
+        return np.where(k * u < 0.5, k * u / (1.0 - np.minimum(k * u, 0.5)), np.inf)
+    if mode == "atomic_f32":
+        derived = gamma(np.maximum(n_e - 1, 0), 2.0 ** -24) * m_plus + n_e * 2.0 ** -25
+    elif mode == "atomic_f16":
+        derived = gamma(n_e, 2.0 ** -11) * m_plus + 2 * n_e * 2.0 ** -25
+    elif mode == "sliced":
+        derived = gamma(n_e + 4, 2.0 ** -11) * m_plus + 17 * 2.0 ** -24 * m_plus + 2 * n_e * 2.0 ** -25
+    else:
+        derived = np.full_like(exact, np.inf)
+        for l in range(16):
+            if ref.hashed[l]:
+                a, b = grid.offset[l], grid.offset[l + 1]
+                assert np.array_equal(grad[a:b].cpu().numpy().view(np.int16), ref.f16_exact[a:b].view(np.int16)), "binned, level %d" % l
+                derived[a:b] = 0.5 * R.ulp16(ref.f16_exact[a:b])
+    err_q = np.abs(got.numpy().astype(np.float64) - exact)
+    limit = np.minimum(derived, tol * scale)
+    worst = np.unravel_index(np.argmax(err_q / np.maximum(limit, 1e-300)), err_q.shape)
+    print("\n%s: worst error / per-entry limit %.3f at entry %d (n_e %d, mass %g); entries held to the derived bound: %.1f %%" % (
+        mode, float(err_q[worst] / max(limit[worst], 1e-300)), worst[0], int(ref.n_e[worst[0]]), float(ref.M_e[worst]), 100.0 * float((derived < tol * scale).mean())))
+    assert (err_q <= limit).all(), (mode, int((err_q > limit).sum()), float(err_q[worst]), float(limit[worst]), int(worst[0]), int(ref.n_e[worst[0]]))
+    assert (got.numpy()[ref.n_e == 0] == 0).all()
 
 
 def outlier_frac(got, want, tol):
@@ -341,11 +384,18 @@ def test_active_sample_compaction(lib, field):
                  128.0, n, a, na, lib.ptr(dh), lib.ptr(dfeats), lib.ptr(partials), lib.stream())
         grad = torch.full((field.meta.total, 2), float("nan"), dtype=torch.float16, device="cuda")
         lib.call("ngp_hashgrid_bwd_sliced", lib.ptr(xs), lib.ptr(mnt), lib.ptr(mxt), lib.ptr(dfeats), C.byref(meta), n, a, na, lib.ptr(grad), lib.stream())
+        binned = torch.full((field.meta.total, 2), float("nan"), dtype=torch.float16, device="cuda")
+        nbytes = lib.lib().ngp_hashgrid_bwd_binned_workspace_bytes(C.byref(meta), n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        lib.call("ngp_hashgrid_bwd_binned", lib.ptr(xs), lib.ptr(mnt), lib.ptr(mxt), lib.ptr(dfeats), C.byref(meta), n, a, na,
+                 lib.ptr(ws), nbytes, lib.ptr(binned), lib.stream())
         wsum = torch.cat([partials[:n_part * 3072].view(n_part, 3072).sum(0), partials[n_part * 3072:].view(n_part, 7168).sum(0)])
-        outs.append((wsum.cpu(), grad.float().cpu()))
-    (w0, g0), (w1, g1) = outs
+        outs.append((wsum.cpu(), grad.float().cpu(), binned.cpu()))
+    (w0, g0, b0), (w1, g1, b1) = outs
     assert ((w0 - w1).abs().max() / w0.abs().max()).item() < 1e-4       # same terms, different partial-sum grouping
     assert ((g0 - g1).abs().max() / g0.abs().max()).item() < 5e-3       # f16 accumulation order differs
+    # binned: the skipped samples carry zero seeds and the sums are integers -- the compacted run IS the full run, bit for bit
+    assert torch.equal(b0.view(torch.int16), b1.view(torch.int16)) and bool(b0.any()) and not torch.isnan(b0.float()).any()
 
 
 # ---------------------------------------------------------------------------------------------------------
