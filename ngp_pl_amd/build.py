@@ -11,6 +11,8 @@
                      (csrc/mesh_compact.h) is shared source of this library, the component filter and the simplifier.
   libngp_meshsimplify.so -- simplification of a mesh by vertex clustering behind include/ngp_meshsimplify.h; its sources
                      live under csrc/meshsimplify/.
+  libngp_meshtsdf.so -- fusion of per-camera depth maps into a truncated signed distance volume on the export lattice behind
+                     include/ngp_meshtsdf.h; its sources live under csrc/meshtsdf/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -49,6 +51,11 @@ MESHSIMPLIFY_SOURCES = [os.path.join("meshsimplify", "meshsimplify.hip")]
 MESHSIMPLIFY_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshsimplify.h")]
 # cells, fixed-point fractions and the f64 means are the plain expressions of include/ngp_meshsimplify.h, as tests/mesh_simplify_reference.py has them
 MESHSIMPLIFY_CFLAGS = ["-ffp-contract=off"]
+MESHTSDF_LIB = os.path.join(CSRC, "libngp_meshtsdf.so")
+MESHTSDF_SOURCES = [os.path.join("meshtsdf", "meshtsdf.hip")]
+MESHTSDF_HEADERS = [os.path.join("..", "..", "include", "ngp_meshtsdf.h")]
+# lattice points, projection and truncated distances are the plain f32 expressions of include/ngp_meshtsdf.h, as tests/mesh_tsdf_reference.py has them
+MESHTSDF_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -83,14 +90,16 @@ def build(force=False, verbose=False):
     filter_objs, filter_jobs = _plan(MESHFILTER_SOURCES, MESHFILTER_HEADERS, lambda src: [], force)
     cull_objs, cull_jobs = _plan(MESHCULL_SOURCES, MESHCULL_HEADERS, lambda src: MESHCULL_CFLAGS, force)
     simplify_objs, simplify_jobs = _plan(MESHSIMPLIFY_SOURCES, MESHSIMPLIFY_HEADERS, lambda src: MESHSIMPLIFY_CFLAGS, force)
-    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs
+    tsdf_objs, tsdf_jobs = _plan(MESHTSDF_SOURCES, MESHTSDF_HEADERS, lambda src: MESHTSDF_CFLAGS, force)
+    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
         with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 1)) as ex:
             list(ex.map(_run, todo))
     for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs), (MESHFILTER_LIB, filter_objs, filter_jobs),
-                            (MESHCULL_LIB, cull_objs, cull_jobs), (MESHSIMPLIFY_LIB, simplify_objs, simplify_jobs)):
+                            (MESHCULL_LIB, cull_objs, cull_jobs), (MESHSIMPLIFY_LIB, simplify_objs, simplify_jobs),
+                            (MESHTSDF_LIB, tsdf_objs, tsdf_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

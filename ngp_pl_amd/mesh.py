@@ -12,11 +12,15 @@
     l = vertex_clusters(m, cell=0.004)                             # (V,) i32: smallest vertex index in the vertex's grid cell
     m = simplify_clusters(m, cell=0.004)                           # one vertex per occupied cell (libngp_meshsimplify.so)
     m = extract_mesh(model, 512, keep_largest=1, simplify_voxels=2, colors=True)     # cells of 2 voxels, after filter and cull
+    d = render_depths(model, K, poses, (W, H))                     # (C, H, W) f32: camera-space z of what each pixel sees, +inf for nothing
+    vol = tsdf_volume(512, (lo3, hi3), K, poses, (W, H), d, trunc=4 * voxel)   # depth maps fused into a TSDF (libngp_meshtsdf.so); level 0
+    m = extract_mesh(model, 512, tsdf=dict(K=K, poses=poses, img_wh=(W, H)), keep_largest=1)     # the surface the renders agree on
     save_ply("mesh.ply", m)
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
                               [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]]
-                              [--simplify-voxels K] --out mesh.ply
+                              [--simplify-voxels K] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
+                              --out mesh.ply
 
 Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
 [k, j, i]; vertices come back in world coordinates.  The reference's notebook (test.ipynb) instead samples
@@ -33,7 +37,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, _mesh_lib, _meshcull_lib, _meshfilter_lib, _meshsimplify_lib
+from . import _lib, _mesh_lib, _meshcull_lib, _meshfilter_lib, _meshsimplify_lib, _meshtsdf_lib
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -347,6 +351,83 @@ def cull_invisible(mesh, K, poses, img_wh, bias, min_views=1, near=NEAR_DISTANCE
     return _cull(v, f, extra, views, min_views)
 
 
+def _lattice_bounds(bounds):
+    """(lo3, hi3) as floats with lo < hi (ValueError otherwise)."""
+    try:
+        lo, hi = [float(v) for v in bounds[0]], [float(v) for v in bounds[1]]
+    except (TypeError, ValueError, IndexError):
+        raise ValueError("bounds must be (lo3, hi3): %r" % (bounds,))
+    if len(lo) != 3 or len(hi) != 3 or any(not (a < b) for a, b in zip(lo, hi)) or not all(math.isfinite(v) for v in lo + hi):
+        raise ValueError("bounds must be (lo3, hi3), finite, with lo < hi: %r" % (bounds,))
+    return lo, hi
+
+
+@torch.no_grad()
+def render_depths(model, K, poses, img_wh, min_opacity=0.5, **render_kwargs):
+    """(C, H, W) f32 on the model's device: for every camera the frame of render(test_time=True) turned into a depth map, depth /
+    opacity where opacity >= min_opacity and +inf elsewhere (a ray that misses the box, or composites too little, met nothing).  The
+    ray directions of get_ray_directions have z = 1, so the depth is the camera-space z that tsdf_volume compares with.  K (3, 3),
+    poses (C, 3, 4) camera-to-world and img_wh = (W, H) are NGP.mark_invisible_cells' arguments; render_kwargs go to render()."""
+    from .rendering import render
+    from .synthetic import get_ray_directions, get_rays
+    _cameras(K, poses, img_wh)
+    _require_cuda(model.xyz_min, "the model")
+    dev = model.xyz_min.device
+    Kd, Pd, W, H = _cameras(K, poses, img_wh, dev)
+    dirs = get_ray_directions(H, W, Kd.cpu(), device=dev)
+    out = torch.empty(Pd.shape[0], H, W, dtype=torch.float32, device=dev)
+    inf = torch.tensor(float("inf"), dtype=torch.float32, device=dev)
+    for c in range(Pd.shape[0]):
+        rays_o, rays_d = get_rays(dirs, Pd[c])
+        r = render(model, rays_o, rays_d, **dict(render_kwargs, test_time=True))
+        depth, opacity = r["depth"].float(), r["opacity"].float()
+        out[c] = torch.where((opacity >= min_opacity) & (opacity > 0), depth / opacity, inf).view(H, W)
+    return out
+
+
+def tsdf_volume(resolution, bounds, K, poses, img_wh, depths, trunc, near=NEAR_DISTANCE, max_cameras_per_call=None, return_state=False):
+    """(nz, ny, nx) f32: the depth maps `depths` (C, H, W) f32 of the cameras K (3, 3), poses (C, 3, 4) camera-to-world, img_wh =
+    (W, H) fused into a truncated signed distance volume on the (nx, ny, nz) lattice over bounds = (lo3, hi3)
+    (include/ngp_meshtsdf.h has the exact rule).  A depth is the camera-space z of what the pixel sees; +inf is a ray that met
+    nothing, NaN, 0 and negatives are no observation.  Space a camera sees through is carved to -1, space within `trunc` (world
+    units) of a seen surface holds the mean of the truncated distances (positive inside), space that was only ever hidden behind
+    a surface is +1: marching_cubes(vol, 0.0, bounds) is the surface.  max_cameras_per_call=N integrates the cameras N at a time;
+    the result does not depend on it.  return_state=True also returns acc (f32), seen (i32) and behind (i32), each (nz, ny, nx).
+    No host sync."""
+    nx, ny, nz = _resolution(resolution)
+    lo, hi = _lattice_bounds(bounds)
+    _cameras(K, poses, img_wh)
+    n_cams = torch.as_tensor(poses).shape[0]
+    W, H = int(img_wh[0]), int(img_wh[1])
+    if not isinstance(depths, torch.Tensor) or depths.dtype != torch.float32 or tuple(depths.shape) != (n_cams, H, W):
+        raise ValueError("depths must be a (C, H, W) = (%d, %d, %d) float32 tensor" % (n_cams, H, W))
+    trunc = float(trunc)
+    if not (math.isfinite(trunc) and trunc > 0 and math.isfinite(C.c_float(trunc).value) and C.c_float(trunc).value > 0):
+        raise ValueError("trunc must be finite and > 0 (as a float32): %r" % (trunc,))
+    per_call = n_cams if max_cameras_per_call is None else int(max_cameras_per_call)
+    if per_call < 1:
+        raise ValueError("max_cameras_per_call must be >= 1: %r" % (max_cameras_per_call,))
+    _require_cuda(depths, "depths")
+    if _meshtsdf_lib.lib().ngp_meshtsdf_state_bytes(nx, ny, nz) == 0:
+        raise ValueError("resolution %r out of range (each axis 2..65535)" % ((nx, ny, nz),))
+    dev = depths.device
+    depths = depths.contiguous()
+    Kd, Pd, W, H = _cameras(K, poses, img_wh, dev)
+    b6 = bounds6(lo, hi)
+    acc = torch.zeros(nz, ny, nx, dtype=torch.float32, device=dev)
+    seen = torch.zeros(nz, ny, nx, dtype=torch.int32, device=dev)
+    behind = torch.zeros(nz, ny, nx, dtype=torch.int32, device=dev)
+    vol = torch.empty_like(acc) if return_state else acc
+    with device_guard(dev):
+        s = stream()
+        for c0 in range(0, n_cams, per_call):
+            n = min(per_call, n_cams - c0)
+            _meshtsdf_lib.call("ngp_meshtsdf_integrate", nx, ny, nz, b6, ptr(Kd), Pd.data_ptr() + 48 * c0, depths.data_ptr() + 4 * W * H * c0,
+                               n, W, H, float(near), trunc, ptr(acc), ptr(seen), ptr(behind), s)
+        _meshtsdf_lib.call("ngp_meshtsdf_finish", acc.numel(), ptr(acc), ptr(seen), ptr(behind), ptr(vol), s)
+    return (vol, acc, seen, behind) if return_state else vol
+
+
 def _grid(cell, origin):
     """cell as a float that is finite and > 0, origin as None or 3 floats (ValueError otherwise)."""
     try:
@@ -429,14 +510,30 @@ def simplify_clusters(mesh, cell, origin=None):
     return _simplify(v, f, extra, cell, origin)[0]
 
 
-def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None, simplify_voxels=None):
+def _tsdf(model, resolution, lo, hi, K, poses, img_wh, trunc_voxels=4.0, min_opacity=0.5, depths=None):
+    """The TSDF volume of extract_mesh(tsdf=dict(...)): the depth maps rendered from the model unless given, trunc in voxels of the
+    largest lattice spacing."""
+    if not (math.isfinite(float(trunc_voxels)) and float(trunc_voxels) > 0):
+        raise ValueError("trunc_voxels must be a finite number > 0: %r" % (trunc_voxels,))
+    _cameras(K, poses, img_wh)
+    if depths is None:
+        depths = render_depths(model, K, poses, img_wh, min_opacity=min_opacity)
+    trunc = float(trunc_voxels) * max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution)))
+    return tsdf_volume(resolution, (lo, hi), K, poses, img_wh, depths, trunc)
+
+
+def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None, simplify_voxels=None, tsdf=None):
     """extract_mesh, (components found, components kept) when a filter option is set (else None), the number of faces the cull
     dropped when `cull` is set (else None), and (V0, V1, F0, F1) around the simplification when simplify_voxels is set (else None)."""
     if simplify_voxels is not None and not (math.isfinite(float(simplify_voxels)) and float(simplify_voxels) > 0):
         raise ValueError("simplify_voxels must be a finite number > 0: %r" % (simplify_voxels,))
     lo, hi = _bounds(model, bounds)
-    vol = density_volume(model, resolution, (lo, hi))
-    m = marching_cubes(vol, threshold, (lo, hi))
+    if tsdf is None:
+        vol = density_volume(model, resolution, (lo, hi))
+        m = marching_cubes(vol, threshold, (lo, hi))
+    else:
+        vol = _tsdf(model, resolution, lo, hi, **tsdf)
+        m = marching_cubes(vol, 0.0, (lo, hi))
     del vol
     found = None
     if keep_largest is not None or min_component_faces is not None:
@@ -465,13 +562,17 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
 
 
 def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None, cull=None,
-                 simplify_voxels=None):
+                 simplify_voxels=None, tsdf=None):
     """density_volume + marching_cubes in the model's world coordinates; keep_largest / min_component_faces filter the components
     (filter_components); cull=dict(K=, poses=, img_wh=, min_views=1, bias=None) then drops the faces none of those cameras sees
     (cull_invisible; bias=None is twice the largest lattice spacing); simplify_voxels=K then merges the vertices of every grid
     cell of K times the largest lattice spacing, the grid starting at the bounds' lower corner (simplify_clusters); colors=True adds
-    vertex_colors, evaluated after all three on the vertices that are left, along minus their (averaged) normals."""
-    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels)[0]
+    vertex_colors, evaluated after all three on the vertices that are left, along minus their (averaged) normals.
+    tsdf=dict(K=, poses=, img_wh=, trunc_voxels=4.0, min_opacity=0.5, depths=None) replaces the first stage: instead of the density
+    thresholded at `threshold` (which is then not used), the volume is tsdf_volume of the depth maps those cameras render
+    (render_depths with min_opacity; or `depths` (C, H, W) f32 when given), truncated at trunc_voxels times the largest lattice
+    spacing, and the iso-level is 0.  The other stages follow unchanged and in the same order."""
+    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels, tsdf)[0]
 
 
 def _np(a):
@@ -524,6 +625,11 @@ def main(argv=None):
     ap.add_argument("--cull-bias", type=float, default=None, metavar="B", help="depth slack in world units (default: two voxels)")
     ap.add_argument("--simplify-voxels", type=float, default=None, metavar="K",
                     help="merge the vertices of every grid cell of K voxels (vertex clustering), after the filter and the cull")
+    ap.add_argument("--tsdf-cameras", default=None, metavar="FILE.npz",
+                    help="mesh the TSDF fusion of the depth maps these cameras render instead of the thresholded density: an .npz as "
+                         "--cull-cameras takes (--threshold is then not used)")
+    ap.add_argument("--tsdf-trunc-voxels", type=float, default=4.0, metavar="T", help="truncation distance of the TSDF in voxels")
+    ap.add_argument("--tsdf-min-opacity", type=float, default=0.5, metavar="O", help="opacity a pixel needs for its depth to count as a surface")
     ap.add_argument("--out", required=True, help="output .ply")
     a = ap.parse_args(argv)
     if len(a.resolution) not in (1, 3):
@@ -532,6 +638,8 @@ def main(argv=None):
         ap.error("--keep-largest takes K >= 0")
     if a.simplify_voxels is not None and not (math.isfinite(a.simplify_voxels) and a.simplify_voxels > 0):
         ap.error("--simplify-voxels takes K > 0")
+    if not (math.isfinite(a.tsdf_trunc_voxels) and a.tsdf_trunc_voxels > 0):
+        ap.error("--tsdf-trunc-voxels takes T > 0")
     from .networks import NGP
     from .utils import load_ckpt
     model = NGP(scale=a.scale, level_table=a.level_table).cuda()
@@ -542,9 +650,17 @@ def main(argv=None):
         with np.load(a.cull_cameras) as cams:
             cull = dict(K=cams["K"], poses=cams["poses"], img_wh=tuple(int(n) for n in cams["img_wh"]), min_views=a.cull_min_views,
                         bias=a.cull_bias)
-    m, found, culled, simplified = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull, a.simplify_voxels)
+    tsdf = None
+    if a.tsdf_cameras is not None:
+        with np.load(a.tsdf_cameras) as cams:
+            tsdf = dict(K=cams["K"], poses=cams["poses"], img_wh=tuple(int(n) for n in cams["img_wh"]), trunc_voxels=a.tsdf_trunc_voxels,
+                        min_opacity=a.tsdf_min_opacity)
+    m, found, culled, simplified = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull, a.simplify_voxels,
+                                            tsdf)
     save_ply(a.out, m)
     line = "%s: %d vertices, %d faces" % (a.out, m.vertices.shape[0], m.faces.shape[0])
+    if tsdf is not None:
+        line += ", tsdf from %d cameras" % len(tsdf["poses"])
     if found is not None:
         line += ", %d components found, %d kept" % found
     if culled is not None:

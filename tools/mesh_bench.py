@@ -15,7 +15,14 @@ The visibility cull is timed on the same mesh: cull_invisible against `--cull-ca
 
 The simplification is timed on the same mesh: simplify_clusters with cells of K = 2 and K = 4 voxels from the box's lower corner
 (as extract_mesh(simplify_voxels=K) calls it), wall time with a device sync, best of `--reps`; V and F before and after.  With
-`--surface-stats N` the vertex-to-surface median / p95 of the N^3 mesh after each."""
+`--surface-stats N` the vertex-to-surface median / p95 of the N^3 mesh after each.
+
+`--tsdf` adds the depth-map fusion: render_depths of the `--cull-cameras` hemisphere poses at `--cull-size`^2 pixels and tsdf_volume
+of them at `--resolution` with a truncation of 4 voxels, each wall time with a device sync, best of `--reps`; the integrator's
+algorithmic bytes (the 12-byte state read and written once, one 4-byte depth per (point, camera) pair that reaches the gather) and
+the number of those pairs.  With `--surface-stats N` V, F, the component count, the largest component's share and the
+vertex-to-surface median / p95 of the N^3 mesh of extract_mesh(tsdf=...) (trunc_voxels 4, min_opacity 0.5), and again after
+keep_largest=1."""
 import argparse
 import json
 import math
@@ -72,6 +79,7 @@ def main():
     ap.add_argument("--surface-stats", type=int, default=0, metavar="N", help="also report the filter's effect on the N^3 mesh")
     ap.add_argument("--cull-cameras", type=int, default=100, metavar="C", help="cameras of the visibility cull")
     ap.add_argument("--cull-size", type=int, default=800, metavar="W", help="image width and height of the visibility cull")
+    ap.add_argument("--tsdf", action="store_true", help="also time render_depths and tsdf_volume, and report the TSDF mesh under --surface-stats")
     a = ap.parse_args()
     torch.manual_seed(2)
     model = NGP(scale=0.5).cuda()
@@ -110,6 +118,16 @@ def main():
     for k in (2, 4):
         t_simplify, small = best_of(a.reps, lambda: mesh.simplify_clusters(m, k * max((h - l) / (n - 1) for l, h in zip(lo, hi)), origin=lo))
         res.update({"simplify_k%d_s" % k: t_simplify, "V_simplified_k%d" % k: small.vertices.shape[0], "F_simplified_k%d" % k: small.faces.shape[0]})
+    depths = None
+    if a.tsdf:
+        t_depths, depths = best_of(min(a.reps, 1), lambda: mesh.render_depths(model, K, poses, wh))
+        trunc = 4.0 * max((h - l) / (n - 1) for l, h in zip(lo, hi))
+        t_tsdf, _ = best_of(a.reps, lambda: mesh.tsdf_volume(n, (lo, hi), K, poses, wh, depths, trunc))
+        _, _, seen_n, behind_n = mesh.tsdf_volume(n, (lo, hi), K, poses, wh, depths, trunc, return_state=True)
+        pairs = int(seen_n.sum(dtype=torch.int64).item() + behind_n.sum(dtype=torch.int64).item())
+        del seen_n, behind_n
+        res.update(render_depths_s=t_depths, tsdf_volume_s=t_tsdf, tsdf_pairs=n ** 3 * a.cull_cameras, tsdf_gather_pairs=pairs,
+                   tsdf_algorithmic_bytes=2 * 12 * n ** 3 + 4 * pairs, depth_pixels_finite=int(torch.isfinite(depths).sum().item()))
     if a.surface_stats:
         ns = a.surface_stats
         ms = mesh.extract_mesh(model, ns, a.threshold)
@@ -134,6 +152,15 @@ def main():
                                 V_seen=mc.vertices.shape[0], F_seen=mc.faces.shape[0], median_voxels_seen=culled[0], p95_voxels_seen=culled[1],
                                 V_kept_seen=mkc.vertices.shape[0], F_kept_seen=mkc.faces.shape[0], median_voxels_kept_seen=both[0],
                                 p95_voxels_kept_seen=both[1], seen_by_min_views=by_min_views))
+        if a.tsdf:
+            mt = mesh.extract_mesh(model, ns, tsdf=dict(K=K, poses=poses, img_wh=wh, trunc_voxels=4.0, min_opacity=0.5, depths=depths))
+            ct = mesh.connected_components(mt)
+            mtk = mesh.filter_components(mt, keep_largest=1)
+            e, ek = surface_error(mt, ns), surface_error(mtk, ns)
+            res["surface"].update(tsdf=dict(V=mt.vertices.shape[0], F=mt.faces.shape[0], C=ct.n_components,
+                                            largest_face_share=ct.faces_per_component.max().item() / mt.faces.shape[0],
+                                            median_voxels=e[0], p95_voxels=e[1], V_kept=mtk.vertices.shape[0], F_kept=mtk.faces.shape[0],
+                                            median_voxels_kept=ek[0], p95_voxels_kept=ek[1]))
     print(json.dumps(res))
 
 
