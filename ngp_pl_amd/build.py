@@ -13,6 +13,8 @@
                      live under csrc/meshsimplify/.
   libngp_meshtsdf.so -- fusion of per-camera depth maps into a truncated signed distance volume on the export lattice behind
                      include/ngp_meshtsdf.h; its sources live under csrc/meshtsdf/.
+  libngp_meshsmooth.so -- Taubin smoothing of a mesh on an integer grid and geometric vertex normals behind
+                     include/ngp_meshsmooth.h; its sources live under csrc/meshsmooth/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -56,6 +58,11 @@ MESHTSDF_SOURCES = [os.path.join("meshtsdf", "meshtsdf.hip")]
 MESHTSDF_HEADERS = [os.path.join("..", "..", "include", "ngp_meshtsdf.h")]
 # lattice points, projection and truncated distances are the plain f32 expressions of include/ngp_meshtsdf.h, as tests/mesh_tsdf_reference.py has them
 MESHTSDF_CFLAGS = ["-ffp-contract=off"]
+MESHSMOOTH_LIB = os.path.join(CSRC, "libngp_meshsmooth.so")
+MESHSMOOTH_SOURCES = [os.path.join("meshsmooth", "meshsmooth.hip")]
+MESHSMOOTH_HEADERS = [os.path.join("..", "..", "include", "ngp_meshsmooth.h")]
+# grid states, the f64 steps and the normals are the plain expressions of include/ngp_meshsmooth.h, as tests/mesh_smooth_reference.py has them
+MESHSMOOTH_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -91,7 +98,8 @@ def build(force=False, verbose=False):
     cull_objs, cull_jobs = _plan(MESHCULL_SOURCES, MESHCULL_HEADERS, lambda src: MESHCULL_CFLAGS, force)
     simplify_objs, simplify_jobs = _plan(MESHSIMPLIFY_SOURCES, MESHSIMPLIFY_HEADERS, lambda src: MESHSIMPLIFY_CFLAGS, force)
     tsdf_objs, tsdf_jobs = _plan(MESHTSDF_SOURCES, MESHTSDF_HEADERS, lambda src: MESHTSDF_CFLAGS, force)
-    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs
+    smooth_objs, smooth_jobs = _plan(MESHSMOOTH_SOURCES, MESHSMOOTH_HEADERS, lambda src: MESHSMOOTH_CFLAGS, force)
+    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -99,7 +107,7 @@ def build(force=False, verbose=False):
             list(ex.map(_run, todo))
     for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs), (MESHFILTER_LIB, filter_objs, filter_jobs),
                             (MESHCULL_LIB, cull_objs, cull_jobs), (MESHSIMPLIFY_LIB, simplify_objs, simplify_jobs),
-                            (MESHTSDF_LIB, tsdf_objs, tsdf_jobs)):
+                            (MESHTSDF_LIB, tsdf_objs, tsdf_jobs), (MESHSMOOTH_LIB, smooth_objs, smooth_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

@@ -15,11 +15,16 @@
     d = render_depths(model, K, poses, (W, H))                     # (C, H, W) f32: camera-space z of what each pixel sees, +inf for nothing
     vol = tsdf_volume(512, (lo3, hi3), K, poses, (W, H), d, trunc=4 * voxel)   # depth maps fused into a TSDF (libngp_meshtsdf.so); level 0
     m = extract_mesh(model, 512, tsdf=dict(K=K, poses=poses, img_wh=(W, H)), keep_largest=1)     # the surface the renders agree on
+    t = mesh_topology(m, cell=voxel)                               # Topology: degree, flags (inside, boundary, free), edge and vertex totals
+    m = smooth_taubin(m, cell=voxel, iterations=10)                # Taubin's lambda|mu filter on an integer grid (libngp_meshsmooth.so)
+    n = vertex_normals(m)                                          # (V, 3) f32: area-free means of the face normals, of the mesh as it is
+    m = extract_mesh(model, 512, keep_largest=1, simplify_voxels=2, smooth=10, colors=True)      # smoothing last, colours from before it
     save_ply("mesh.ply", m)
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
                               [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]]
                               [--simplify-voxels K] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
+                              [--smooth-iterations N [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]]
                               --out mesh.ply
 
 Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
@@ -37,7 +42,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, _mesh_lib, _meshcull_lib, _meshfilter_lib, _meshsimplify_lib, _meshtsdf_lib
+from . import _lib, _mesh_lib, _meshcull_lib, _meshfilter_lib, _meshsimplify_lib, _meshsmooth_lib, _meshtsdf_lib
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -510,6 +515,131 @@ def simplify_clusters(mesh, cell, origin=None):
     return _simplify(v, f, extra, cell, origin)[0]
 
 
+@dataclasses.dataclass
+class Topology:
+    degree: object              # (V,) i32: the number of distinct neighbours; 0 for a vertex outside the grid
+    flags: object               # (V,) u8: bit 0 inside the grid, bit 1 on a boundary edge, bit 2 free (smoothing moves it)
+    n_edges: int
+    n_boundary_edges: int       # edges that occur in exactly one face
+    n_free: int
+    n_boundary_vertices: int
+
+
+def _smooth_args(iterations, lam, mu):
+    """iterations as an int >= 0, lam and mu as floats that are finite with magnitude <= 1 (ValueError otherwise)."""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0 or iterations > INT32_MAX:
+        raise ValueError("iterations must be an int >= 0: %r" % (iterations,))
+    out = []
+    for name, x in (("lam", lam), ("mu", mu)):
+        try:
+            x = float(x)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number: %r" % (name, x))
+        if not (math.isfinite(x) and abs(x) <= 1.0):
+            raise ValueError("%s must be finite with magnitude <= 1: %r" % (name, x))
+        out.append(x)
+    return int(iterations), out[0], out[1]
+
+
+def _topology(v, f, cell, origin, pin_boundary):
+    """ngp_meshsmooth_topology -> degree (V,) i32, flags (V,) u8, totals (4,) i64 on the device, the workspace (which holds the
+    neighbour lists) and the origin on the device.  V > 0."""
+    n_v, n_f, dev = v.shape[0], f.shape[0], v.device
+    if origin is None:
+        o = v.amin(0)                                    # on the device: no sync
+    else:
+        o = torch.as_tensor(origin, dtype=torch.float32).reshape(3).to(dev)
+    o = o.contiguous()
+    degree = torch.empty(n_v, dtype=torch.int32, device=dev)
+    flags = torch.empty(n_v, dtype=torch.uint8, device=dev)
+    totals = torch.empty(4, dtype=torch.int64, device=dev)
+    ws_bytes = _meshsmooth_lib.lib().ngp_meshsmooth_workspace_bytes(n_v, n_f)
+    with device_guard(dev):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _meshsmooth_lib.call("ngp_meshsmooth_topology", ptr(v), ptr(f), n_v, n_f, ptr(o), cell, int(bool(pin_boundary)), ptr(ws), ws_bytes,
+                             ptr(degree), ptr(flags), ptr(totals), stream())
+    return degree, flags, totals, ws, ws_bytes, o
+
+
+def mesh_topology(mesh, cell, origin=None, pin_boundary=True):
+    """Topology of the mesh as smooth_taubin sees it (include/ngp_meshsmooth.h has the exact rule): an edge is a side of a face
+    with three different indices in range whose two ends are inside the grid of quantum cell / 65536 around `origin` (3 floats;
+    None: the vertices' minimum per axis, taken on the device), at most 2^14 cells away from it; the degree of a vertex is the
+    number of its distinct neighbours; a boundary edge occurs in exactly one face; a vertex is free when it is inside, has a
+    neighbour and, with pin_boundary, is on no boundary edge.  One host sync for the four totals."""
+    cell, origin = _grid(cell, origin)
+    v, f, _ = _check_mesh(mesh)
+    if v.shape[0] == 0:
+        return Topology(torch.empty(0, dtype=torch.int32, device=v.device), torch.empty(0, dtype=torch.uint8, device=v.device), 0, 0, 0, 0)
+    degree, flags, totals, _, _, _ = _topology(v, f, cell, origin, pin_boundary)
+    return Topology(degree, flags, *totals.tolist())
+
+
+def _normals(v, f, ws=None, ws_bytes=0):
+    """ngp_meshsmooth_normals -> (V, 3) f32; ws: a workspace of ngp_meshsmooth_workspace_bytes(V, F) to reuse.  V > 0."""
+    n_v, n_f, dev = v.shape[0], f.shape[0], v.device
+    out = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+    with device_guard(dev):
+        if ws is None:
+            ws_bytes = _meshsmooth_lib.lib().ngp_meshsmooth_workspace_bytes(n_v, n_f)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _meshsmooth_lib.call("ngp_meshsmooth_normals", ptr(v), ptr(f), n_v, n_f, ptr(ws), ws_bytes, ptr(out), stream())
+    return out
+
+
+def vertex_normals(mesh):
+    """(V, 3) f32: the geometric normals of the mesh as it is -- per vertex the normalised sum of the unit normals of its faces,
+    each added in 2^-20 fixed point so that the result is the same on every run (include/ngp_meshsmooth.h); all zeros for a
+    vertex of no face, or of faces that cancel.  Degenerate faces and faces with a non-finite corner add nothing.
+    Counter-clockwise faces give outward normals, as marching_cubes' gradient normals are.  No host sync."""
+    v, f, _ = _check_mesh(mesh)
+    if v.shape[0] == 0:
+        return torch.empty(0, 3, dtype=torch.float32, device=v.device)
+    return _normals(v, f)
+
+
+def _smooth(v, f, extra, cell, origin, iterations, lam, mu, pin_boundary, recompute_normals):
+    """topology, taubin, normals -> the smoothed Mesh and the topology's totals (4,) i64 on the device (None when nothing ran)."""
+    normals, colors = extra
+    if v.shape[0] == 0 or iterations == 0:
+        return Mesh(v.clone(), f.clone(), None if normals is None else normals.clone(), None if colors is None else colors.clone()), None
+    _, _, totals, ws, ws_bytes, o = _topology(v, f, cell, origin, pin_boundary)
+    out = torch.empty_like(v)
+    with device_guard(v.device):
+        _meshsmooth_lib.call("ngp_meshsmooth_taubin", ptr(v), v.shape[0], f.shape[0], ptr(o), cell, iterations, lam, mu, ptr(ws), ws_bytes,
+                             ptr(out), stream())
+    if normals is not None:
+        normals = _normals(out, f, ws, ws_bytes) if recompute_normals else normals.clone()
+    return Mesh(out, f.clone(), normals, None if colors is None else colors.clone()), totals
+
+
+def smooth_taubin(mesh, cell, iterations=10, lam=0.5, mu=-0.53, origin=None, pin_boundary=True, recompute_normals=True):
+    """The mesh after `iterations` pairs of Taubin's filter: a Laplacian pass with factor lam, then one with factor mu (negative,
+    a little larger in magnitude: the pair removes the noise without shrinking the object).  The passes run on an integer grid of
+    quantum cell / 65536 around `origin` (3 floats; None: the vertices' minimum, taken on the device) with exact int64 neighbour
+    sums, so the result is the same on every run and for any order of the faces (include/ngp_meshsmooth.h has the exact rule).
+    Free vertices (mesh_topology) move; with pin_boundary the ends of boundary edges keep their words bit for bit, as do vertices
+    of no face and vertices that are not finite or more than 2^14 cells from the origin.  Faces and colours are copied; normals
+    are recomputed as vertex_normals of the result when the input has normals and recompute_normals is set, else copied.
+    iterations=0 returns a copy.  Mesh-only: the field is not read.  No host sync."""
+    cell, origin = _grid(cell, origin)
+    iterations, lam, mu = _smooth_args(iterations, lam, mu)
+    v, f, extra = _check_mesh(mesh)
+    return _smooth(v, f, extra, cell, origin, iterations, lam, mu, pin_boundary, recompute_normals)[0]
+
+
+def _smooth_options(smooth):
+    """extract_mesh's `smooth`: None, an int (iterations) or a dict -> None or checked keyword arguments of _smooth."""
+    if smooth is None:
+        return None
+    opts = dict(smooth) if isinstance(smooth, dict) else dict(iterations=smooth)
+    unknown = set(opts) - {"iterations", "lam", "mu", "pin_boundary"}
+    if unknown:
+        raise ValueError("smooth: unknown keys %r" % sorted(unknown))
+    iterations, lam, mu = _smooth_args(opts.get("iterations", 10), opts.get("lam", 0.5), opts.get("mu", -0.53))
+    return dict(iterations=iterations, lam=lam, mu=mu, pin_boundary=bool(opts.get("pin_boundary", True)))
+
+
 def _tsdf(model, resolution, lo, hi, K, poses, img_wh, trunc_voxels=4.0, min_opacity=0.5, depths=None):
     """The TSDF volume of extract_mesh(tsdf=dict(...)): the depth maps rendered from the model unless given, trunc in voxels of the
     largest lattice spacing."""
@@ -522,9 +652,12 @@ def _tsdf(model, resolution, lo, hi, K, poses, img_wh, trunc_voxels=4.0, min_opa
     return tsdf_volume(resolution, (lo, hi), K, poses, img_wh, depths, trunc)
 
 
-def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None, simplify_voxels=None, tsdf=None):
+def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None, simplify_voxels=None, tsdf=None,
+             smooth=None):
     """extract_mesh, (components found, components kept) when a filter option is set (else None), the number of faces the cull
-    dropped when `cull` is set (else None), and (V0, V1, F0, F1) around the simplification when simplify_voxels is set (else None)."""
+    dropped when `cull` is set (else None), (V0, V1, F0, F1) around the simplification when simplify_voxels is set (else None), and
+    (pairs, the topology's totals (4,) i64 on the device or None) when `smooth` is set (else None)."""
+    smooth = _smooth_options(smooth)
     if simplify_voxels is not None and not (math.isfinite(float(simplify_voxels)) and float(simplify_voxels) > 0):
         raise ValueError("simplify_voxels must be a finite number > 0: %r" % (simplify_voxels,))
     lo, hi = _bounds(model, bounds)
@@ -558,11 +691,17 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
         simplified = (before[0], m.vertices.shape[0], before[1], m.faces.shape[0])
     if colors:
         m.colors = vertex_colors(model, m.vertices, m.normals)
-    return m, found, culled, simplified
+    smoothed = None
+    if smooth is not None:
+        cell, _ = _grid(max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution))), None)
+        v, f, extra = _check_mesh(m)
+        m, totals = _smooth(v, f, extra, cell, lo, recompute_normals=True, **smooth)
+        smoothed = (smooth["iterations"], totals)
+    return m, found, culled, simplified, smoothed
 
 
 def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None, cull=None,
-                 simplify_voxels=None, tsdf=None):
+                 simplify_voxels=None, tsdf=None, smooth=None):
     """density_volume + marching_cubes in the model's world coordinates; keep_largest / min_component_faces filter the components
     (filter_components); cull=dict(K=, poses=, img_wh=, min_views=1, bias=None) then drops the faces none of those cameras sees
     (cull_invisible; bias=None is twice the largest lattice spacing); simplify_voxels=K then merges the vertices of every grid
@@ -571,8 +710,12 @@ def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=Fals
     tsdf=dict(K=, poses=, img_wh=, trunc_voxels=4.0, min_opacity=0.5, depths=None) replaces the first stage: instead of the density
     thresholded at `threshold` (which is then not used), the volume is tsdf_volume of the depth maps those cameras render
     (render_depths with min_opacity; or `depths` (C, H, W) f32 when given), truncated at trunc_voxels times the largest lattice
-    spacing, and the iso-level is 0.  The other stages follow unchanged and in the same order."""
-    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels, tsdf)[0]
+    spacing, and the iso-level is 0.  The other stages follow unchanged and in the same order.
+    smooth=N, or dict(iterations=10, lam=0.5, mu=-0.53, pin_boundary=True), adds smooth_taubin as the last geometric stage, on the
+    grid of the largest lattice spacing that starts at the bounds' lower corner; the normals become vertex_normals of the smoothed
+    mesh.  Colours are then still evaluated BEFORE the smoothing, on the surface the field defines and along minus the gradient
+    normals, and are carried through."""
+    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels, tsdf, smooth)[0]
 
 
 def _np(a):
@@ -630,6 +773,11 @@ def main(argv=None):
                          "--cull-cameras takes (--threshold is then not used)")
     ap.add_argument("--tsdf-trunc-voxels", type=float, default=4.0, metavar="T", help="truncation distance of the TSDF in voxels")
     ap.add_argument("--tsdf-min-opacity", type=float, default=0.5, metavar="O", help="opacity a pixel needs for its depth to count as a surface")
+    ap.add_argument("--smooth-iterations", type=int, default=None, metavar="N",
+                    help="smooth the mesh with N pairs of Taubin's lambda|mu filter, as the last geometric stage; normals become geometric")
+    ap.add_argument("--smooth-lambda", type=float, default=0.5, metavar="L", help="factor of the first pass of a pair, magnitude <= 1")
+    ap.add_argument("--smooth-mu", type=float, default=-0.53, metavar="M", help="factor of the second pass of a pair, magnitude <= 1")
+    ap.add_argument("--smooth-free-boundary", action="store_true", help="let the vertices of boundary edges move too")
     ap.add_argument("--out", required=True, help="output .ply")
     a = ap.parse_args(argv)
     if len(a.resolution) not in (1, 3):
@@ -640,6 +788,11 @@ def main(argv=None):
         ap.error("--simplify-voxels takes K > 0")
     if not (math.isfinite(a.tsdf_trunc_voxels) and a.tsdf_trunc_voxels > 0):
         ap.error("--tsdf-trunc-voxels takes T > 0")
+    if a.smooth_iterations is not None and a.smooth_iterations < 0:
+        ap.error("--smooth-iterations takes N >= 0")
+    for flag, x in (("--smooth-lambda", a.smooth_lambda), ("--smooth-mu", a.smooth_mu)):
+        if not (math.isfinite(x) and abs(x) <= 1):
+            ap.error("%s takes a finite factor of magnitude <= 1" % flag)
     from .networks import NGP
     from .utils import load_ckpt
     model = NGP(scale=a.scale, level_table=a.level_table).cuda()
@@ -655,8 +808,11 @@ def main(argv=None):
         with np.load(a.tsdf_cameras) as cams:
             tsdf = dict(K=cams["K"], poses=cams["poses"], img_wh=tuple(int(n) for n in cams["img_wh"]), trunc_voxels=a.tsdf_trunc_voxels,
                         min_opacity=a.tsdf_min_opacity)
-    m, found, culled, simplified = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull, a.simplify_voxels,
-                                            tsdf)
+    smooth = None
+    if a.smooth_iterations is not None:
+        smooth = dict(iterations=a.smooth_iterations, lam=a.smooth_lambda, mu=a.smooth_mu, pin_boundary=not a.smooth_free_boundary)
+    m, found, culled, simplified, smoothed = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull,
+                                                      a.simplify_voxels, tsdf, smooth)
     save_ply(a.out, m)
     line = "%s: %d vertices, %d faces" % (a.out, m.vertices.shape[0], m.faces.shape[0])
     if tsdf is not None:
@@ -667,6 +823,9 @@ def main(argv=None):
         line += ", %d faces culled as unseen" % culled
     if simplified is not None:
         line += ", simplified %d -> %d vertices, %d -> %d faces" % simplified
+    if smoothed is not None:
+        n_free = 0 if smoothed[1] is None else int(smoothed[1][2].item())
+        line += ", smoothed %d pairs, %d of %d vertices free" % (smoothed[0], n_free, m.vertices.shape[0])
     print(line)
     return 0
 

@@ -17,6 +17,11 @@ The simplification is timed on the same mesh: simplify_clusters with cells of K 
 (as extract_mesh(simplify_voxels=K) calls it), wall time with a device sync, best of `--reps`; V and F before and after.  With
 `--surface-stats N` the vertex-to-surface median / p95 of the N^3 mesh after each.
 
+The smoothing is timed on the same mesh, on the grid of one voxel from the box's lower corner (as extract_mesh(smooth=...) calls
+it): ngp_meshsmooth_topology (the edge table, the degrees and the neighbour lists), ten Taubin pairs (twenty gather passes) on
+those lists, and vertex_normals, each wall time with a device sync, best of `--reps`; the edge count and the free vertices.  For
+scale, the same ten pairs as torch.index_add_ of float32 positions over the same directed edges (built outside the timing).
+
 `--tsdf` adds the depth-map fusion: render_depths of the `--cull-cameras` hemisphere poses at `--cull-size`^2 pixels and tsdf_volume
 of them at `--resolution` with a truncation of 4 voxels, each wall time with a device sync, best of `--reps`; the integrator's
 algorithmic bytes (the 12-byte state read and written once, one 4-byte depth per (point, camera) pair that reaches the gather) and
@@ -70,6 +75,43 @@ def best_of(reps, fn):
     return best, out
 
 
+def smoothing(m, cell, lo, reps):
+    """Times of the three calls of libngp_meshsmooth.so on mesh m, and of ten pairs done with torch.index_add_ in float32."""
+    from ngp_pl_amd import _meshsmooth_lib as L
+    v, f, _ = mesh._check_mesh(m)
+    cell, _ = mesh._grid(cell, None)
+    t_topology, (degree, flags, totals, ws, ws_bytes, o) = best_of(reps, lambda: mesh._topology(v, f, cell, lo, True))
+    out = torch.empty_like(v)
+
+    def pairs():
+        with L.device_guard(v.device):
+            L.call("ngp_meshsmooth_taubin", L.ptr(v), v.shape[0], f.shape[0], L.ptr(o), cell, 10, 0.5, -0.53, L.ptr(ws), ws_bytes, L.ptr(out), L.stream())
+
+    t_pairs, _ = best_of(reps, pairs)
+    t_normals, _ = best_of(reps, lambda: mesh.vertex_normals(mesh.Mesh(out, f)))
+    # the same edges and the same free vertices, float32 positions, one index_add_ per pass
+    fl = f.long()
+    e = torch.cat([fl[:, [0, 1]], fl[:, [1, 2]], fl[:, [2, 0]]])
+    e = torch.unique(torch.cat([e, e.flip(1)]), dim=0)
+    src, dst = e[:, 0].contiguous(), e[:, 1].contiguous()
+    free = ((flags & 4) != 0).unsqueeze(1)
+    deg = degree.clamp(min=1).float().unsqueeze(1)
+
+    def eager():
+        x = v
+        for _ in range(10):
+            for factor in (0.5, -0.53):
+                s = torch.zeros_like(x).index_add_(0, dst, x[src])
+                x = torch.where(free, x + factor * (s / deg - x), x)
+        return x
+
+    t_eager, x = best_of(reps, eager)
+    n_edges, n_boundary, n_free, _ = totals.tolist()
+    return dict(smooth_topology_s=t_topology, smooth_10_pairs_s=t_pairs, smooth_normals_s=t_normals, smooth_10_pairs_index_add_f32_s=t_eager,
+                smooth_edges=n_edges, smooth_boundary_edges=n_boundary, smooth_free_vertices=n_free, smooth_max_degree=int(degree.max().item()),
+                smooth_max_abs_difference_to_index_add_voxels=float((x - out).abs().max().item() / cell))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=2000)
@@ -118,6 +160,7 @@ def main():
     for k in (2, 4):
         t_simplify, small = best_of(a.reps, lambda: mesh.simplify_clusters(m, k * max((h - l) / (n - 1) for l, h in zip(lo, hi)), origin=lo))
         res.update({"simplify_k%d_s" % k: t_simplify, "V_simplified_k%d" % k: small.vertices.shape[0], "F_simplified_k%d" % k: small.faces.shape[0]})
+    res.update(smoothing(m, max((h - l) / (n - 1) for l, h in zip(lo, hi)), lo, a.reps))
     depths = None
     if a.tsdf:
         t_depths, depths = best_of(min(a.reps, 1), lambda: mesh.render_depths(model, K, poses, wh))
