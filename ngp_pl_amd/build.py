@@ -15,6 +15,8 @@
                      include/ngp_meshtsdf.h; its sources live under csrc/meshtsdf/.
   libngp_meshsmooth.so -- Taubin smoothing of a mesh on an integer grid and geometric vertex normals behind
                      include/ngp_meshsmooth.h; its sources live under csrc/meshsmooth/.
+  libngp_meshtex.so -- the texture atlas of a mesh (layout, texel points, UVs) and the renderer of the textured mesh behind
+                     include/ngp_meshtex.h; its sources live under csrc/meshtex/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -63,6 +65,11 @@ MESHSMOOTH_SOURCES = [os.path.join("meshsmooth", "meshsmooth.hip")]
 MESHSMOOTH_HEADERS = [os.path.join("..", "..", "include", "ngp_meshsmooth.h")]
 # grid states, the f64 steps and the normals are the plain expressions of include/ngp_meshsmooth.h, as tests/mesh_smooth_reference.py has them
 MESHSMOOTH_CFLAGS = ["-ffp-contract=off"]
+MESHTEX_LIB = os.path.join(CSRC, "libngp_meshtex.so")
+MESHTEX_SOURCES = [os.path.join("meshtex", "meshtex.hip")]
+MESHTEX_HEADERS = [os.path.join("..", "..", "include", "ngp_meshtex.h")]
+# texel points, directions, projection, barycentric weights and the bilinear lookup are the plain f32 expressions of include/ngp_meshtex.h, as tests/mesh_texture_reference.py has them
+MESHTEX_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -99,7 +106,8 @@ def build(force=False, verbose=False):
     simplify_objs, simplify_jobs = _plan(MESHSIMPLIFY_SOURCES, MESHSIMPLIFY_HEADERS, lambda src: MESHSIMPLIFY_CFLAGS, force)
     tsdf_objs, tsdf_jobs = _plan(MESHTSDF_SOURCES, MESHTSDF_HEADERS, lambda src: MESHTSDF_CFLAGS, force)
     smooth_objs, smooth_jobs = _plan(MESHSMOOTH_SOURCES, MESHSMOOTH_HEADERS, lambda src: MESHSMOOTH_CFLAGS, force)
-    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs
+    tex_objs, tex_jobs = _plan(MESHTEX_SOURCES, MESHTEX_HEADERS, lambda src: MESHTEX_CFLAGS, force)
+    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -107,7 +115,8 @@ def build(force=False, verbose=False):
             list(ex.map(_run, todo))
     for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs), (MESHFILTER_LIB, filter_objs, filter_jobs),
                             (MESHCULL_LIB, cull_objs, cull_jobs), (MESHSIMPLIFY_LIB, simplify_objs, simplify_jobs),
-                            (MESHTSDF_LIB, tsdf_objs, tsdf_jobs), (MESHSMOOTH_LIB, smooth_objs, smooth_jobs)):
+                            (MESHTSDF_LIB, tsdf_objs, tsdf_jobs), (MESHSMOOTH_LIB, smooth_objs, smooth_jobs),
+                            (MESHTEX_LIB, tex_objs, tex_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

@@ -19,13 +19,20 @@
     m = smooth_taubin(m, cell=voxel, iterations=10)                # Taubin's lambda|mu filter on an integer grid (libngp_meshsmooth.so)
     n = vertex_normals(m)                                          # (V, 3) f32: area-free means of the face normals, of the mesh as it is
     m = extract_mesh(model, 512, keep_largest=1, simplify_voxels=2, smooth=10, colors=True)      # smoothing last, colours from before it
+    t = texture_atlas(m, texels=8)                                 # Texture: the atlas layout (two faces per cell) and the UVs (libngp_meshtex.so)
+    p, d, ok = texel_points(m, t, box)                             # world point, viewing direction and validity of every texel
+    m = bake_texture(model, m, texels=8)                           # the field's colour at every texel -> m.texture.image (H, W, 3) u8
+    img = render_textured(m, K, poses, (W, H))                     # (C, H, W, 3) f32: the textured mesh seen from the cameras
+    m = extract_mesh(model, 512, keep_largest=1, simplify_voxels=2, smooth=10, texture=8)        # baked after the simplification, before the smoothing
     save_ply("mesh.ply", m)
+    save_obj("mesh.obj", m)                                        # mesh.obj + mesh.mtl + mesh.png (needs m.texture with an image)
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
                               [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]]
                               [--simplify-voxels K] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
                               [--smooth-iterations N [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]]
-                              --out mesh.ply
+                              [--texture-texels T]
+                              --out mesh.ply | mesh.obj
 
 Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
 [k, j, i]; vertices come back in world coordinates.  The reference's notebook (test.ipynb) instead samples
@@ -37,12 +44,15 @@ import argparse
 import ctypes as C
 import dataclasses
 import math
+import os
+import struct
 import sys
+import zlib
 
 import numpy as np
 import torch
 
-from . import _lib, _mesh_lib, _meshcull_lib, _meshfilter_lib, _meshsimplify_lib, _meshsmooth_lib, _meshtsdf_lib
+from . import _lib, _mesh_lib, _meshcull_lib, _meshfilter_lib, _meshsimplify_lib, _meshsmooth_lib, _meshtex_lib, _meshtsdf_lib
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -55,6 +65,7 @@ class Mesh:
     faces: object               # (F, 3) i32, counter-clockwise seen from outside
     normals: object = None      # (V, 3) f32, unit, outward (density falls outward); 0 where the gradient vanishes
     colors: object = None       # (V, 3) f32 RGB in [0, 1], or None
+    texture: object = None      # Texture (atlas layout, per-face UVs, image), or None
 
 
 def _resolution(resolution):
@@ -628,6 +639,181 @@ def smooth_taubin(mesh, cell, iterations=10, lam=0.5, mu=-0.53, origin=None, pin
     return _smooth(v, f, extra, cell, origin, iterations, lam, mu, pin_boundary, recompute_normals)[0]
 
 
+@dataclasses.dataclass
+class Texture:
+    texels: int                 # T: texel intervals along a face's leg
+    width: int                  # atlas width in texels
+    height: int
+    cells_per_row: int          # cells of (T + 5) x (T + 4) texels, two faces each
+    uvs: object                 # (F, 3, 2) f32: u, v of every face's corners, OBJ's bottom-left origin
+    image: object = None        # (H, W, 3) u8, row 0 on top; None before baking
+
+
+def _texels(texels):
+    if isinstance(texels, bool) or not isinstance(texels, (int, np.integer)) or not 1 <= texels <= 256:
+        raise ValueError("texels must be an int in 1..256: %r" % (texels,))
+    return int(texels)
+
+
+def _atlas(n_faces, texels):
+    """ngp_meshtex_atlas_size -> (cells_per_row, W, H); ValueError when the atlas does not fit 16384 x 16384 texels."""
+    if n_faces < 1:
+        raise ValueError("the mesh has no faces: there is nothing to put into an atlas")
+    c, w, h = C.c_int(), C.c_int(), C.c_int()
+    rc = _meshtex_lib.lib().ngp_meshtex_atlas_size(n_faces, texels, C.byref(c), C.byref(w), C.byref(h))
+    if rc == -5:
+        raise ValueError("an atlas of %d faces at %d texels is wider or higher than 16384 texels: lower texels or simplify the mesh" % (n_faces, texels))
+    if rc != 0:
+        raise _lib.NgpError("ngp_meshtex_atlas_size failed: %d" % rc)
+    return c.value, w.value, h.value
+
+
+def texture_atlas(mesh, texels=8):
+    """The atlas layout and the UVs of the mesh's faces (include/ngp_meshtex.h has the exact rule): every face is a right triangle
+    with legs of `texels` texel intervals, two faces to a cell of (texels + 5) x (texels + 4) texels with a one-texel extrapolated
+    border round each, the cells in rows that make the atlas about square.  Returns a Texture without an image.  No host sync."""
+    texels = _texels(texels)
+    if isinstance(mesh.faces, torch.Tensor) and mesh.faces.dim() == 2 and mesh.faces.shape[0] == 0:
+        raise ValueError("the mesh has no faces: there is nothing to put into an atlas")
+    v, f, _ = _check_mesh(mesh)
+    c, w, h = _atlas(f.shape[0], texels)
+    uvs = torch.empty(f.shape[0], 3, 2, dtype=torch.float32, device=v.device)
+    with device_guard(v.device):
+        _meshtex_lib.call("ngp_meshtex_face_uvs", f.shape[0], texels, ptr(uvs), stream())
+    return Texture(texels, w, h, c, uvs)
+
+
+def _box6(box):
+    """(lo3, hi3) -> six floats, finite with lo <= hi (ValueError otherwise)."""
+    try:
+        lo, hi = [float(x) for x in box[0]], [float(x) for x in box[1]]
+    except (TypeError, ValueError, IndexError):
+        raise ValueError("box must be (lo3, hi3): %r" % (box,))
+    if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(x) for x in lo + hi) or any(a > b for a, b in zip(lo, hi)):
+        raise ValueError("box must be (lo3, hi3), finite, with lo <= hi: %r" % (box,))
+    return (C.c_float * 6)(*(lo + hi))
+
+
+def _texel_points(v, f, normals, texture, b6, begin, count, out=None):
+    dev = v.device
+    if out is None:
+        out = (torch.empty(count, 3, dtype=torch.float32, device=dev), torch.empty(count, 3, dtype=torch.float32, device=dev),
+               torch.empty(count, dtype=torch.uint8, device=dev))
+    with device_guard(dev):
+        _meshtex_lib.call("ngp_meshtex_texel_points", ptr(v), ptr(f), ptr(normals), v.shape[0], f.shape[0], texture.texels, b6, begin, count,
+                          ptr(out[0]), ptr(out[1]), ptr(out[2]), stream())
+    return out
+
+
+def _check_texture(texture, n_faces):
+    if not isinstance(texture, Texture):
+        raise ValueError("texture must be a Texture (texture_atlas, bake_texture): %r" % (texture,))
+    texels = _texels(texture.texels)
+    if (texture.cells_per_row, texture.width, texture.height) != _atlas(n_faces, texels):
+        raise ValueError("the texture's layout is not the atlas of %d faces at %d texels" % (n_faces, texels))
+    return texels
+
+
+def texel_points(mesh, texture, box, begin=0, count=None):
+    """(points (n, 3) f32, dirs (n, 3) f32, valid (n,) u8) of texels begin .. begin+count-1 of the row-major atlas (default: all):
+    the world point of the texel on its face, clamped to box = (lo3, hi3), the direction minus the interpolated vertex normal
+    ((0, 0, 1) where that is zero or not finite), and whether the texel belongs to a face with indices in range and a finite
+    point.  mesh.normals must be set.  No host sync."""
+    v, f, extra = _check_mesh(mesh)
+    _check_texture(texture, f.shape[0])
+    if extra[0] is None:
+        raise ValueError("mesh.normals must be set: the texel directions come from them (vertex_normals(mesh) gives geometric ones)")
+    b6 = _box6(box)
+    n = texture.width * texture.height
+    count = n - begin if count is None else count
+    if begin < 0 or count < 0 or begin + count > n:
+        raise ValueError("begin %r, count %r leave the atlas of %d texels" % (begin, count, n))
+    return _texel_points(v, f, extra[0], texture, b6, int(begin), int(count))
+
+
+def _quantise(c):
+    """round(clamp(c, 0, 1) * 255) as u8, halves to even; NaN is 0."""
+    return torch.round(torch.clamp(torch.nan_to_num(c.float(), nan=0.0), 0.0, 1.0) * 255.0).to(torch.uint8)
+
+
+@torch.no_grad()
+def bake_texture(model, mesh, texels=8, chunk=1 << 20, color_fn=None, box=None):
+    """The mesh with .texture set: texture_atlas(mesh, texels) with the colour of every texel, evaluated `chunk` texels at a time
+    at texel_points (inside the model's box; or `box` = (lo3, hi3), needed when model is None) by the model's no-grad forward, as
+    vertex_colors uses it, or by color_fn(points (n, 3), dirs (n, 3)) -> (n, 3).  The image stores round(clamp(c, 0, 1) * 255),
+    halves to even, and 0 for invalid texels.  If mesh.normals is None the directions come from vertex_normals(mesh)."""
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError("chunk must be an int >= 1: %r" % (chunk,))
+    if model is None and (color_fn is None or box is None):
+        raise ValueError("without a model both color_fn and box are needed")
+    t = texture_atlas(mesh, texels)
+    v, f, extra = _check_mesh(mesh)
+    normals = extra[0] if extra[0] is not None else _normals(v, f)
+    b6 = _box6(box if box is not None else _box(model))
+    n = t.width * t.height
+    image = torch.empty(n, 3, dtype=torch.uint8, device=v.device)
+    chunk = int(min(chunk, n))
+    buf = None
+    for begin in range(0, n, chunk):
+        cnt = min(chunk, n - begin)
+        if buf is not None and buf[0].shape[0] != cnt:   # the last, shorter chunk
+            buf = None
+        buf = p, d, ok = _texel_points(v, f, normals, t, b6, begin, cnt, buf)
+        rgb = color_fn(p, d) if color_fn is not None else model(p, d)[1]
+        if not isinstance(rgb, torch.Tensor) or tuple(rgb.shape) != (cnt, 3):
+            raise ValueError("the colour evaluator must return a (%d, 3) tensor" % cnt)
+        image[begin:begin + cnt] = _quantise(rgb) * ok.unsqueeze(1)
+    t.image = image.view(t.height, t.width, 3)
+    return dataclasses.replace(mesh, texture=t)
+
+
+def render_textured(mesh, K, poses, img_wh, background=(1, 1, 1), near=NEAR_DISTANCE, max_workspace_bytes=1 << 28, return_ids=False):
+    """(C, H, W, 3) f32: the mesh with its baked texture seen from the cameras K (3, 3), poses (C, 3, 4) camera-to-world, img_wh =
+    (W, H) -- NGP.mark_invisible_cells' arguments.  Per pixel the nearest face that covers its centre (the cull's rasteriser rule;
+    at equal depth the smaller face index), its texture looked up bilinearly at the perspective-correct point; `background` where
+    no face lands (include/ngp_meshtex.h has the exact rule).  The cameras go through a key buffer of 8 bytes per pixel, as many
+    at a time as fit max_workspace_bytes (at least one); the result does not depend on that.  return_ids=True also returns the
+    face index (C, H, W) i32 (-1 for none) and the depth (C, H, W) f32 (+inf for none).  No host sync."""
+    _cameras(K, poses, img_wh)
+    v, f, _ = _check_mesh(mesh)
+    texels = _check_texture(mesh.texture, f.shape[0])
+    img = mesh.texture.image
+    if (not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or tuple(img.shape) != (mesh.texture.height, mesh.texture.width, 3)):
+        raise ValueError("mesh.texture.image must be a (H, W, 3) uint8 tensor: bake_texture sets it")
+    _require_cuda(img, "mesh.texture.image")
+    img = img.contiguous()
+    try:
+        bg = [float(x) for x in background]
+        near = float(near)
+    except (TypeError, ValueError):
+        raise ValueError("background must be three numbers and near a number")
+    if len(bg) != 3 or not all(math.isfinite(x) for x in bg) or not math.isfinite(near):
+        raise ValueError("background must be three finite numbers and near finite: %r, %r" % (background, near))
+    dev = v.device
+    Kd, Pd, W, H = _cameras(K, poses, img_wh, dev)
+    n_cams = Pd.shape[0]
+    fit = max(1, min(n_cams, int(max_workspace_bytes) // (8 * W * H)))
+    image = torch.empty(n_cams, H, W, 3, dtype=torch.float32, device=dev)
+    ids = torch.empty(n_cams, H, W, dtype=torch.int32, device=dev) if return_ids else None
+    depth = torch.empty(n_cams, H, W, dtype=torch.float32, device=dev) if return_ids else None
+    with device_guard(dev):
+        ws = torch.empty(fit, H, W, dtype=torch.int64, device=dev)
+        _meshtex_lib.call("ngp_meshtex_render", ptr(v), ptr(f), v.shape[0], f.shape[0], texels, ptr(img), ptr(Kd), ptr(Pd), n_cams,
+                          W, H, near, (C.c_float * 3)(*bg), ptr(ws), ws.numel() * 8, ptr(image), ptr(ids), ptr(depth), stream())
+    return (image, ids, depth) if return_ids else image
+
+
+def _texture_options(texture):
+    """extract_mesh's `texture`: None, an int (texels) or dict(texels=) -> None or the checked texels."""
+    if texture is None:
+        return None
+    opts = dict(texture) if isinstance(texture, dict) else dict(texels=texture)
+    unknown = set(opts) - {"texels"}
+    if unknown:
+        raise ValueError("texture: unknown keys %r" % sorted(unknown))
+    return _texels(opts.get("texels", 8))
+
+
 def _smooth_options(smooth):
     """extract_mesh's `smooth`: None, an int (iterations) or a dict -> None or checked keyword arguments of _smooth."""
     if smooth is None:
@@ -653,11 +839,12 @@ def _tsdf(model, resolution, lo, hi, K, poses, img_wh, trunc_voxels=4.0, min_opa
 
 
 def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None, simplify_voxels=None, tsdf=None,
-             smooth=None):
-    """extract_mesh, (components found, components kept) when a filter option is set (else None), the number of faces the cull
+             smooth=None, texture=None):
+    """extract_mesh (with `texture`: baked after the simplification and the colours, before the smoothing), (components found, components kept) when a filter option is set (else None), the number of faces the cull
     dropped when `cull` is set (else None), (V0, V1, F0, F1) around the simplification when simplify_voxels is set (else None), and
     (pairs, the topology's totals (4,) i64 on the device or None) when `smooth` is set (else None)."""
     smooth = _smooth_options(smooth)
+    texture = _texture_options(texture)
     if simplify_voxels is not None and not (math.isfinite(float(simplify_voxels)) and float(simplify_voxels) > 0):
         raise ValueError("simplify_voxels must be a finite number > 0: %r" % (simplify_voxels,))
     lo, hi = _bounds(model, bounds)
@@ -691,17 +878,22 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
         simplified = (before[0], m.vertices.shape[0], before[1], m.faces.shape[0])
     if colors:
         m.colors = vertex_colors(model, m.vertices, m.normals)
+    baked = None
+    if texture is not None:
+        baked = bake_texture(model, m, texture).texture
     smoothed = None
     if smooth is not None:
         cell, _ = _grid(max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution))), None)
         v, f, extra = _check_mesh(m)
         m, totals = _smooth(v, f, extra, cell, lo, recompute_normals=True, **smooth)
         smoothed = (smooth["iterations"], totals)
+    if baked is not None:
+        m.texture = baked
     return m, found, culled, simplified, smoothed
 
 
 def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None, cull=None,
-                 simplify_voxels=None, tsdf=None, smooth=None):
+                 simplify_voxels=None, tsdf=None, smooth=None, texture=None):
     """density_volume + marching_cubes in the model's world coordinates; keep_largest / min_component_faces filter the components
     (filter_components); cull=dict(K=, poses=, img_wh=, min_views=1, bias=None) then drops the faces none of those cameras sees
     (cull_invisible; bias=None is twice the largest lattice spacing); simplify_voxels=K then merges the vertices of every grid
@@ -714,8 +906,13 @@ def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=Fals
     smooth=N, or dict(iterations=10, lam=0.5, mu=-0.53, pin_boundary=True), adds smooth_taubin as the last geometric stage, on the
     grid of the largest lattice spacing that starts at the bounds' lower corner; the normals become vertex_normals of the smoothed
     mesh.  Colours are then still evaluated BEFORE the smoothing, on the surface the field defines and along minus the gradient
-    normals, and are carried through."""
-    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels, tsdf, smooth)[0]
+    normals, and are carried through.
+    texture=T, or dict(texels=T), adds bake_texture with T texels per face leg: after the simplification, and BEFORE the smoothing if
+    there is any -- the faces do not change under smoothing, so the baked texture belongs to the smoothed mesh, and the texels are
+    sampled on the surface the field defines and along minus the gradient normals, the rule `colors` follows.  Without it
+    mesh.texture is None and everything else is the same bits."""
+    return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels, tsdf, smooth,
+                    texture)[0]
 
 
 def _np(a):
@@ -752,8 +949,51 @@ def save_ply(path, m):
         out.write(frec.tobytes())
 
 
+def _png(image):
+    """The bytes of an 8-bit RGB PNG of image (H, W, 3) u8: filter 0 on every row, one IDAT chunk."""
+    h, w, _ = image.shape
+    chunk = lambda tag, data: struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), image.reshape(h, w * 3)], 1).tobytes()
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw, 6))
+            + chunk(b"IEND", b""))
+
+
+def save_obj(path, m):
+    """Wavefront OBJ with its material and texture: `path`, and beside it the same name with .mtl and .png.  v per vertex, vn per
+    vertex when normals exist, vt three per face (m.texture.uvs), f v/vt/vn (v/vt without normals) one-based, mtllib, usemtl, and
+    map_Kd naming the PNG (8-bit RGB, m.texture.image).  Floats are written with 9 significant digits: they read back to the same
+    float32.  Standard library and numpy only."""
+    t = m.texture
+    if t is None or t.image is None:
+        raise ValueError("save_obj needs a baked texture: mesh.texture with an image (bake_texture, extract_mesh(texture=T))")
+    v = _np(m.vertices).astype(np.float32).reshape(-1, 3)
+    f = _np(m.faces).astype(np.int64).reshape(-1, 3)
+    uv = _np(t.uvs).astype(np.float32).reshape(-1, 2)
+    image = np.ascontiguousarray(_np(t.image), np.uint8)
+    if len(uv) != 3 * len(f) or image.shape != (t.height, t.width, 3):
+        raise ValueError("the texture does not belong to this mesh: %d uvs for %d faces, image %r" % (len(uv), len(f), image.shape))
+    stem = os.path.splitext(path)[0]
+    name = os.path.basename(stem)
+    lines = ["# %d vertices, %d faces, texture %d x %d" % (len(v), len(f), t.width, t.height), "mtllib %s.mtl" % name, "usemtl %s" % name]
+    lines += ["v %.9g %.9g %.9g" % tuple(x) for x in v.tolist()]
+    if m.normals is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(x) for x in _np(m.normals).astype(np.float32).reshape(-1, 3).tolist()]
+    lines += ["vt %.9g %.9g" % tuple(x) for x in uv.tolist()]
+    k = 3 * np.arange(len(f))[:, None] + np.arange(1, 4)[None]
+    if m.normals is not None:
+        lines += ["f %d/%d/%d %d/%d/%d %d/%d/%d" % (a + 1, ta, a + 1, b + 1, tb, b + 1, c + 1, tc, c + 1) for (a, b, c), (ta, tb, tc) in zip(f.tolist(), k.tolist())]
+    else:
+        lines += ["f %d/%d %d/%d %d/%d" % (a + 1, ta, b + 1, tb, c + 1, tc) for (a, b, c), (ta, tb, tc) in zip(f.tolist(), k.tolist())]
+    with open(path, "w") as out:
+        out.write("\n".join(lines) + "\n")
+    with open(stem + ".mtl", "w") as out:
+        out.write("newmtl %s\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s.png\n" % (name, name))
+    with open(stem + ".png", "wb") as out:
+        out.write(_png(image))
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m ngp_pl_amd.mesh", description="Extract a mesh from a trained checkpoint (binary PLY).")
+    ap = argparse.ArgumentParser(prog="python -m ngp_pl_amd.mesh", description="Extract a mesh from a trained checkpoint (binary PLY, or OBJ + MTL + PNG with a texture).")
     ap.add_argument("--ckpt", required=True, help="checkpoint (Lightning .ckpt or a slim state dict)")
     ap.add_argument("--scale", type=float, default=0.5, help="scene scale the model was trained with")
     ap.add_argument("--level-table", default="float32", choices=("float32", "exact"), help="hash-grid level table of the checkpoint")
@@ -778,7 +1018,9 @@ def main(argv=None):
     ap.add_argument("--smooth-lambda", type=float, default=0.5, metavar="L", help="factor of the first pass of a pair, magnitude <= 1")
     ap.add_argument("--smooth-mu", type=float, default=-0.53, metavar="M", help="factor of the second pass of a pair, magnitude <= 1")
     ap.add_argument("--smooth-free-boundary", action="store_true", help="let the vertices of boundary edges move too")
-    ap.add_argument("--out", required=True, help="output .ply")
+    ap.add_argument("--texture-texels", type=int, default=None, metavar="T",
+                    help="bake a texture atlas with T texels along every face's leg (1..256); needs an --out that ends in .obj")
+    ap.add_argument("--out", required=True, help="output .ply, or .obj (written with its .mtl and .png; needs --texture-texels)")
     a = ap.parse_args(argv)
     if len(a.resolution) not in (1, 3):
         ap.error("--resolution takes N or nx ny nz")
@@ -793,6 +1035,13 @@ def main(argv=None):
     for flag, x in (("--smooth-lambda", a.smooth_lambda), ("--smooth-mu", a.smooth_mu)):
         if not (math.isfinite(x) and abs(x) <= 1):
             ap.error("%s takes a finite factor of magnitude <= 1" % flag)
+    obj = a.out.lower().endswith(".obj")
+    if a.texture_texels is not None and not obj:
+        ap.error("--texture-texels needs an --out that ends in .obj: a PLY carries no texture")
+    if obj and a.texture_texels is None:
+        ap.error("an .obj output needs --texture-texels T")
+    if a.texture_texels is not None and not 1 <= a.texture_texels <= 256:
+        ap.error("--texture-texels takes T in 1..256")
     from .networks import NGP
     from .utils import load_ckpt
     model = NGP(scale=a.scale, level_table=a.level_table).cuda()
@@ -812,8 +1061,11 @@ def main(argv=None):
     if a.smooth_iterations is not None:
         smooth = dict(iterations=a.smooth_iterations, lam=a.smooth_lambda, mu=a.smooth_mu, pin_boundary=not a.smooth_free_boundary)
     m, found, culled, simplified, smoothed = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull,
-                                                      a.simplify_voxels, tsdf, smooth)
-    save_ply(a.out, m)
+                                                      a.simplify_voxels, tsdf, smooth, a.texture_texels)
+    if obj:
+        save_obj(a.out, m)
+    else:
+        save_ply(a.out, m)
     line = "%s: %d vertices, %d faces" % (a.out, m.vertices.shape[0], m.faces.shape[0])
     if tsdf is not None:
         line += ", tsdf from %d cameras" % len(tsdf["poses"])
@@ -826,6 +1078,8 @@ def main(argv=None):
     if smoothed is not None:
         n_free = 0 if smoothed[1] is None else int(smoothed[1][2].item())
         line += ", smoothed %d pairs, %d of %d vertices free" % (smoothed[0], n_free, m.vertices.shape[0])
+    if m.texture is not None:
+        line += ", texture %d x %d" % (m.texture.width, m.texture.height)
     print(line)
     return 0
 

@@ -27,7 +27,15 @@ of them at `--resolution` with a truncation of 4 voxels, each wall time with a d
 algorithmic bytes (the 12-byte state read and written once, one 4-byte depth per (point, camera) pair that reaches the gather) and
 the number of those pairs.  With `--surface-stats N` V, F, the component count, the largest component's share and the
 vertex-to-surface median / p95 of the N^3 mesh of extract_mesh(tsdf=...) (trunc_voxels 4, min_opacity 0.5), and again after
-keep_largest=1."""
+keep_largest=1.
+
+`--texture` adds the texture atlas: on the mesh simplified at K = 2, with `--texture-texels` (8) texels per face leg, the wall times
+with a device sync (best of `--reps`) of bake_texture, split into the texel points (ngp_meshtex_texel_points over the whole atlas)
+and the field evaluation with the quantisation (the rest), of render_textured for the `--cull-cameras` hemisphere poses at
+`--cull-size`^2 pixels, and the PSNR of those renders against the field's own test-time render() from the same cameras (both on a
+white background), over all pixels, over the pixels the mesh covers, and over those of them where the field's render is opaque
+too (opacity >= 0.5), with the shares of the pixels in each set, and over the last set the median absolute difference between the
+mesh's depth and the field's (depth / opacity), in world units."""
 import argparse
 import json
 import math
@@ -112,6 +120,53 @@ def smoothing(m, cell, lo, reps):
                 smooth_max_abs_difference_to_index_add_voxels=float((x - out).abs().max().item() / cell))
 
 
+def texturing(model, m, texels, K, poses, wh, reps):
+    """Times of bake_texture (texel points / field evaluation) and render_textured on mesh m, and the PSNR against render()."""
+    from ngp_pl_amd.rendering import render
+    v, f, extra = mesh._check_mesh(m)
+    t_atlas, tex = best_of(reps, lambda: mesh.texture_atlas(m, texels))
+    n = tex.width * tex.height
+    b6 = mesh._box6(mesh._box(model))
+    t_points, (_, _, ok) = best_of(reps, lambda: mesh._texel_points(v, f, extra[0], tex, b6, 0, n))
+    n_valid = int(ok.sum().item())
+    del ok
+    t_bake, baked = best_of(reps, lambda: mesh.bake_texture(model, m, texels))
+    t_render, images = best_of(reps, lambda: mesh.render_textured(baked, K, poses, wh, return_ids=True))
+    image, ids, depth = images
+    dz = []
+    W, H = wh
+    dirs = syn.get_ray_directions(H, W, K, device=v.device)
+    se_all = se_cov = se_both = 0.0
+    n_cov = n_both = n_opaque = 0
+    with torch.no_grad():
+        for c in range(len(poses)):
+            ro, rd = syn.get_rays(dirs, torch.as_tensor(poses[c]).to(device=v.device, dtype=torch.float32).contiguous())
+            r = render(model, ro, rd, test_time=True)
+            want = r["rgb"].float().view(H, W, 3)
+            opaque = r["opacity"].float().view(H, W) >= 0.5                      # the field, too, sees a surface there
+            d2 = (image[c] - want).double().pow(2)
+            cov = ids[c] >= 0
+            se_all += d2.sum().item()
+            se_cov += d2[cov].sum().item()
+            se_both += d2[cov & opaque].sum().item()
+            n_cov += int(cov.sum().item())
+            n_both += int((cov & opaque).sum().item())
+            n_opaque += int(opaque.sum().item())
+            both = cov & opaque
+            if both.any():                                                       # the field's depth, as render_depths forms it
+                z = (r["depth"].float() / r["opacity"].float()).view(H, W)
+                dz.append((depth[c][both] - z[both]).abs())
+    n_all = len(poses) * W * H
+    psnr = lambda se, cnt: float("inf") if se == 0 else -10.0 * math.log10(se / (3 * max(cnt, 1)))
+    return dict(texture_texels=texels, texture_width=tex.width, texture_height=tex.height, texture_texels_total=n, texture_texels_valid=n_valid,
+                texture_faces=f.shape[0], texture_atlas_s=t_atlas, texture_texel_points_s=t_points, bake_texture_s=t_bake,
+                bake_field_evaluation_s=t_bake - t_points - t_atlas, render_textured_s=t_render, render_cameras=len(poses), render_size=W,
+                render_covered_share=n_cov / n_all, render_field_opaque_share=n_opaque / n_all, render_covered_and_opaque_share=n_both / n_all,
+                psnr_vs_field_render_db=psnr(se_all, n_all), psnr_vs_field_render_covered_db=psnr(se_cov, n_cov),
+                psnr_vs_field_render_covered_and_opaque_db=psnr(se_both, n_both),
+                depth_abs_difference_to_field_median=float(torch.cat(dz).median().item()) if dz else None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=2000)
@@ -122,6 +177,8 @@ def main():
     ap.add_argument("--cull-cameras", type=int, default=100, metavar="C", help="cameras of the visibility cull")
     ap.add_argument("--cull-size", type=int, default=800, metavar="W", help="image width and height of the visibility cull")
     ap.add_argument("--tsdf", action="store_true", help="also time render_depths and tsdf_volume, and report the TSDF mesh under --surface-stats")
+    ap.add_argument("--texture", action="store_true", help="also time bake_texture and render_textured on the K = 2 mesh, with the PSNR against render()")
+    ap.add_argument("--texture-texels", type=int, default=8, metavar="T", help="texels per face leg of --texture")
     a = ap.parse_args()
     torch.manual_seed(2)
     model = NGP(scale=0.5).cuda()
@@ -161,6 +218,9 @@ def main():
         t_simplify, small = best_of(a.reps, lambda: mesh.simplify_clusters(m, k * max((h - l) / (n - 1) for l, h in zip(lo, hi)), origin=lo))
         res.update({"simplify_k%d_s" % k: t_simplify, "V_simplified_k%d" % k: small.vertices.shape[0], "F_simplified_k%d" % k: small.faces.shape[0]})
     res.update(smoothing(m, max((h - l) / (n - 1) for l, h in zip(lo, hi)), lo, a.reps))
+    if a.texture:
+        small = mesh.simplify_clusters(m, 2 * max((h - l) / (n - 1) for l, h in zip(lo, hi)), origin=lo)
+        res.update(texturing(model, small, a.texture_texels, K, poses, wh, min(a.reps, 2)))
     depths = None
     if a.tsdf:
         t_depths, depths = best_of(min(a.reps, 1), lambda: mesh.render_depths(model, K, poses, wh))
