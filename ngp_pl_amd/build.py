@@ -17,6 +17,8 @@
                      include/ngp_meshsmooth.h; its sources live under csrc/meshsmooth/.
   libngp_meshtex.so -- the texture atlas of a mesh (layout, texel points, UVs) and the renderer of the textured mesh behind
                      include/ngp_meshtex.h; its sources live under csrc/meshtex/.
+  libngp_metrics.so -- image metrics (the squared error behind PSNR, and SSIM with the Gaussian window) behind
+                     include/ngp_metrics.h; its sources live under csrc/metrics/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -70,6 +72,11 @@ MESHTEX_SOURCES = [os.path.join("meshtex", "meshtex.hip")]
 MESHTEX_HEADERS = [os.path.join("..", "..", "include", "ngp_meshtex.h")]
 # texel points, directions, projection, barycentric weights and the bilinear lookup are the plain f32 expressions of include/ngp_meshtex.h, as tests/mesh_texture_reference.py has them
 MESHTEX_CFLAGS = ["-ffp-contract=off"]
+METRICS_LIB = os.path.join(CSRC, "libngp_metrics.so")
+METRICS_SOURCES = [os.path.join("metrics", "metrics.hip")]
+METRICS_HEADERS = [os.path.join("..", "..", "include", "ngp_metrics.h")]
+# the filter taps, the index and the squared error are the plain f32 expressions of include/ngp_metrics.h, as tests/metrics_reference.py has them
+METRICS_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -107,7 +114,8 @@ def build(force=False, verbose=False):
     tsdf_objs, tsdf_jobs = _plan(MESHTSDF_SOURCES, MESHTSDF_HEADERS, lambda src: MESHTSDF_CFLAGS, force)
     smooth_objs, smooth_jobs = _plan(MESHSMOOTH_SOURCES, MESHSMOOTH_HEADERS, lambda src: MESHSMOOTH_CFLAGS, force)
     tex_objs, tex_jobs = _plan(MESHTEX_SOURCES, MESHTEX_HEADERS, lambda src: MESHTEX_CFLAGS, force)
-    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs
+    metrics_objs, metrics_jobs = _plan(METRICS_SOURCES, METRICS_HEADERS, lambda src: METRICS_CFLAGS, force)
+    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -116,7 +124,7 @@ def build(force=False, verbose=False):
     for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs), (MESHFILTER_LIB, filter_objs, filter_jobs),
                             (MESHCULL_LIB, cull_objs, cull_jobs), (MESHSIMPLIFY_LIB, simplify_objs, simplify_jobs),
                             (MESHTSDF_LIB, tsdf_objs, tsdf_jobs), (MESHSMOOTH_LIB, smooth_objs, smooth_jobs),
-                            (MESHTEX_LIB, tex_objs, tex_jobs)):
+                            (MESHTEX_LIB, tex_objs, tex_jobs), (METRICS_LIB, metrics_objs, metrics_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

@@ -24,6 +24,7 @@
     m = bake_texture(model, m, texels=8)                           # the field's colour at every texel -> m.texture.image (H, W, 3) u8
     img = render_textured(m, K, poses, (W, H))                     # (C, H, W, 3) f32: the textured mesh seen from the cameras
     m = extract_mesh(model, 512, keep_largest=1, simplify_voxels=2, smooth=10, texture=8)        # baked after the simplification, before the smoothing
+    r = compare_renders(model, m, K, poses, (W, H))                # PSNR and SSIM of the textured mesh's renders against the field's (libngp_metrics.so)
     save_ply("mesh.ply", m)
     save_obj("mesh.obj", m)                                        # mesh.obj + mesh.mtl + mesh.png (needs m.texture with an image)
 
@@ -31,7 +32,7 @@
                               [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]]
                               [--simplify-voxels K] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
                               [--smooth-iterations N [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]]
-                              [--texture-texels T]
+                              [--texture-texels T [--score-cameras CAMS.npz [--score-out FILE.json]]]
                               --out mesh.ply | mesh.obj
 
 Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
@@ -803,6 +804,73 @@ def render_textured(mesh, K, poses, img_wh, background=(1, 1, 1), near=NEAR_DIST
     return (image, ids, depth) if return_ids else image
 
 
+SCORE_REGIONS = ("all", "covered", "covered_and_opaque")
+
+
+def compare_renders(model, textured_mesh, K, poses, img_wh, background=(1, 1, 1), data_range=1.0, return_images=False, **render_kwargs):
+    """Scores a textured mesh against the field it was exported from: render_textured(..., return_ids=True) and the field's own
+    render(test_time=True) from the same cameras K (3, 3), poses (C, 3, 4) camera-to-world, img_wh = (W, H) with W, H >= 11, then
+    PSNR and SSIM (ngp_pl_amd.metrics) of the mesh's frames against the field's over three regions: "all" pixels, "covered"
+    (the mesh lands there: ids >= 0) and "covered_and_opaque" (covered, and the field's opacity is >= 0.5).  Returns a dict:
+    cameras, width, height; per region psnr_<region> and ssim_<region> over all cameras (sums and counts pooled), share_<region>
+    of the pixels, and per_camera[<region>] = dict(psnr=[...], ssim=[...]); share_field_opaque; depth_abs_difference_median, the
+    median over the last region of |mesh depth - field depth| with the field's depth formed as render_depths forms it (depth /
+    opacity), None where the region is empty.  return_images=True adds images (C, H, W, 3), ids, depth (render_textured's),
+    field_images (C, H, W, 3), field_opacity and field_depth (C, H, W), all on the device.  render_kwargs go to render().  One
+    host read."""
+    from . import metrics
+    from .rendering import render
+    from .synthetic import get_ray_directions, get_rays
+    _require_cuda(model.xyz_min, "the model")
+    image, ids, depth = render_textured(textured_mesh, K, poses, img_wh, background=background, return_ids=True)
+    dev = image.device
+    Kd, Pd, W, H = _cameras(K, poses, img_wh, dev)
+    n_cams = Pd.shape[0]
+    dirs = get_ray_directions(H, W, Kd.cpu(), device=dev)
+    field = torch.empty(n_cams, H, W, 3, dtype=torch.float32, device=dev)
+    opacity = torch.empty(n_cams, H, W, dtype=torch.float32, device=dev)
+    field_depth = torch.empty(n_cams, H, W, dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for c in range(n_cams):
+            rays_o, rays_d = get_rays(dirs, Pd[c])
+            r = render(model, rays_o, rays_d, **dict(render_kwargs, test_time=True))
+            field[c] = r["rgb"].float().view(H, W, 3)
+            opacity[c] = r["opacity"].float().view(H, W)
+            field_depth[c] = (r["depth"].float() / r["opacity"].float()).view(H, W)
+    covered = ids >= 0
+    both = covered & (opacity >= 0.5)
+    masks = dict(zip(SCORE_REGIONS, (None, covered, both)))
+    rows = []
+    for region in SCORE_REGIONS:
+        se, n_se = metrics.sq_error(image, field, masks[region])
+        total, count = metrics.ssim_sums(image, field, data_range, masks[region])
+        rows += [se, n_se.double(), total, count.double()]
+    dz = (depth[both] - field_depth[both]).abs()
+    median = dz.median().double().view(1) if dz.numel() else torch.full((1,), float("nan"), dtype=torch.float64, device=dev)
+    shares = torch.stack([covered.sum(), both.sum(), (opacity >= 0.5).sum()]).double()
+    host = torch.cat([torch.stack(rows).view(-1), shares, median]).cpu().tolist()                      # the one host read
+    ratio = lambda a, b: a / b if b else float("nan")
+
+    def psnr(se, cnt):
+        if cnt == 0:
+            return float("nan")
+        return float("inf") if se == 0 else 10.0 * math.log10(float(data_range) ** 2 / (se / cnt))
+
+    n_all = n_cams * W * H
+    res = dict(cameras=n_cams, width=W, height=H, per_camera={})
+    for k, region in enumerate(SCORE_REGIONS):
+        se, n_se, total, count = (host[(4 * k + j) * n_cams:(4 * k + j + 1) * n_cams] for j in range(4))
+        res["psnr_" + region] = psnr(sum(se), sum(n_se))
+        res["ssim_" + region] = ratio(math.fsum(total), sum(count))
+        res["per_camera"][region] = dict(psnr=[psnr(a, b) for a, b in zip(se, n_se)], ssim=[ratio(a, b) for a, b in zip(total, count)])
+    n_cov, n_both, n_opaque, med = host[12 * n_cams:]
+    res.update(share_all=1.0, share_covered=n_cov / n_all, share_covered_and_opaque=n_both / n_all, share_field_opaque=n_opaque / n_all,
+               depth_abs_difference_median=None if math.isnan(med) else med)
+    if return_images:
+        res.update(images=image, ids=ids, depth=depth, field_images=field, field_opacity=opacity, field_depth=field_depth)
+    return res
+
+
 def _texture_options(texture):
     """extract_mesh's `texture`: None, an int (texels) or dict(texels=) -> None or the checked texels."""
     if texture is None:
@@ -1020,6 +1088,10 @@ def main(argv=None):
     ap.add_argument("--smooth-free-boundary", action="store_true", help="let the vertices of boundary edges move too")
     ap.add_argument("--texture-texels", type=int, default=None, metavar="T",
                     help="bake a texture atlas with T texels along every face's leg (1..256); needs an --out that ends in .obj")
+    ap.add_argument("--score-cameras", default=None, metavar="FILE.npz",
+                    help="score the textured mesh against the field's own renders from these cameras (PSNR, SSIM; compare_renders) and "
+                         "print the record as one JSON line: an .npz as --cull-cameras takes; needs --texture-texels")
+    ap.add_argument("--score-out", default=None, metavar="FILE.json", help="also write the record of --score-cameras to this file")
     ap.add_argument("--out", required=True, help="output .ply, or .obj (written with its .mtl and .png; needs --texture-texels)")
     a = ap.parse_args(argv)
     if len(a.resolution) not in (1, 3):
@@ -1042,6 +1114,10 @@ def main(argv=None):
         ap.error("an .obj output needs --texture-texels T")
     if a.texture_texels is not None and not 1 <= a.texture_texels <= 256:
         ap.error("--texture-texels takes T in 1..256")
+    if a.score_cameras is not None and a.texture_texels is None:
+        ap.error("--score-cameras needs --texture-texels: the score is of the textured mesh")
+    if a.score_out is not None and a.score_cameras is None:
+        ap.error("--score-out needs --score-cameras")
     from .networks import NGP
     from .utils import load_ckpt
     model = NGP(scale=a.scale, level_table=a.level_table).cuda()
@@ -1081,6 +1157,15 @@ def main(argv=None):
     if m.texture is not None:
         line += ", texture %d x %d" % (m.texture.width, m.texture.height)
     print(line)
+    if a.score_cameras is not None:
+        import json
+        with np.load(a.score_cameras) as cams:
+            record = compare_renders(model, m, cams["K"], cams["poses"], tuple(int(n) for n in cams["img_wh"]))
+        text = json.dumps(record)
+        if a.score_out is not None:
+            with open(a.score_out, "w") as f:
+                f.write(text + "\n")
+        print(text)
     return 0
 
 

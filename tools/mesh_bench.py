@@ -32,10 +32,10 @@ keep_largest=1.
 `--texture` adds the texture atlas: on the mesh simplified at K = 2, with `--texture-texels` (8) texels per face leg, the wall times
 with a device sync (best of `--reps`) of bake_texture, split into the texel points (ngp_meshtex_texel_points over the whole atlas)
 and the field evaluation with the quantisation (the rest), of render_textured for the `--cull-cameras` hemisphere poses at
-`--cull-size`^2 pixels, and the PSNR of those renders against the field's own test-time render() from the same cameras (both on a
-white background), over all pixels, over the pixels the mesh covers, and over those of them where the field's render is opaque
-too (opacity >= 0.5), with the shares of the pixels in each set, and over the last set the median absolute difference between the
-mesh's depth and the field's (depth / opacity), in world units."""
+`--cull-size`^2 pixels, and the PSNR and SSIM (mesh.compare_renders, with its wall time) of those renders against the field's own
+test-time render() from the same cameras (both on a white background), over all pixels, over the pixels the mesh covers, and over
+those of them where the field's render is opaque too (opacity >= 0.5), with the shares of the pixels in each set, and over the
+last set the median absolute difference between the mesh's depth and the field's (depth / opacity), in world units."""
 import argparse
 import json
 import math
@@ -121,8 +121,8 @@ def smoothing(m, cell, lo, reps):
 
 
 def texturing(model, m, texels, K, poses, wh, reps):
-    """Times of bake_texture (texel points / field evaluation) and render_textured on mesh m, and the PSNR against render()."""
-    from ngp_pl_amd.rendering import render
+    """Times of bake_texture (texel points / field evaluation) and render_textured on mesh m, and mesh.compare_renders' PSNR and
+    SSIM against render() with its wall time (both renders of every camera included)."""
     v, f, extra = mesh._check_mesh(m)
     t_atlas, tex = best_of(reps, lambda: mesh.texture_atlas(m, texels))
     n = tex.width * tex.height
@@ -132,39 +132,22 @@ def texturing(model, m, texels, K, poses, wh, reps):
     del ok
     t_bake, baked = best_of(reps, lambda: mesh.bake_texture(model, m, texels))
     t_render, images = best_of(reps, lambda: mesh.render_textured(baked, K, poses, wh, return_ids=True))
-    image, ids, depth = images
-    dz = []
-    W, H = wh
-    dirs = syn.get_ray_directions(H, W, K, device=v.device)
-    se_all = se_cov = se_both = 0.0
-    n_cov = n_both = n_opaque = 0
-    with torch.no_grad():
-        for c in range(len(poses)):
-            ro, rd = syn.get_rays(dirs, torch.as_tensor(poses[c]).to(device=v.device, dtype=torch.float32).contiguous())
-            r = render(model, ro, rd, test_time=True)
-            want = r["rgb"].float().view(H, W, 3)
-            opaque = r["opacity"].float().view(H, W) >= 0.5                      # the field, too, sees a surface there
-            d2 = (image[c] - want).double().pow(2)
-            cov = ids[c] >= 0
-            se_all += d2.sum().item()
-            se_cov += d2[cov].sum().item()
-            se_both += d2[cov & opaque].sum().item()
-            n_cov += int(cov.sum().item())
-            n_both += int((cov & opaque).sum().item())
-            n_opaque += int(opaque.sum().item())
-            both = cov & opaque
-            if both.any():                                                       # the field's depth, as render_depths forms it
-                z = (r["depth"].float() / r["opacity"].float()).view(H, W)
-                dz.append((depth[c][both] - z[both]).abs())
-    n_all = len(poses) * W * H
-    psnr = lambda se, cnt: float("inf") if se == 0 else -10.0 * math.log10(se / (3 * max(cnt, 1)))
+    del images
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    score = mesh.compare_renders(model, baked, K, poses, wh)                     # renders both, scores on the device, one host read
+    t_compare = time.perf_counter() - t0
+    W = wh[0]
     return dict(texture_texels=texels, texture_width=tex.width, texture_height=tex.height, texture_texels_total=n, texture_texels_valid=n_valid,
                 texture_faces=f.shape[0], texture_atlas_s=t_atlas, texture_texel_points_s=t_points, bake_texture_s=t_bake,
                 bake_field_evaluation_s=t_bake - t_points - t_atlas, render_textured_s=t_render, render_cameras=len(poses), render_size=W,
-                render_covered_share=n_cov / n_all, render_field_opaque_share=n_opaque / n_all, render_covered_and_opaque_share=n_both / n_all,
-                psnr_vs_field_render_db=psnr(se_all, n_all), psnr_vs_field_render_covered_db=psnr(se_cov, n_cov),
-                psnr_vs_field_render_covered_and_opaque_db=psnr(se_both, n_both),
-                depth_abs_difference_to_field_median=float(torch.cat(dz).median().item()) if dz else None)
+                render_covered_share=score["share_covered"], render_field_opaque_share=score["share_field_opaque"],
+                render_covered_and_opaque_share=score["share_covered_and_opaque"],
+                psnr_vs_field_render_db=score["psnr_all"], psnr_vs_field_render_covered_db=score["psnr_covered"],
+                psnr_vs_field_render_covered_and_opaque_db=score["psnr_covered_and_opaque"],
+                ssim_vs_field_render=score["ssim_all"], ssim_vs_field_render_covered=score["ssim_covered"],
+                ssim_vs_field_render_covered_and_opaque=score["ssim_covered_and_opaque"], compare_renders_s=t_compare,
+                depth_abs_difference_to_field_median=score["depth_abs_difference_median"])
 
 
 def main():
