@@ -19,6 +19,9 @@
                      include/ngp_meshtex.h; its sources live under csrc/meshtex/.
   libngp_metrics.so -- image metrics (the squared error behind PSNR, and SSIM with the Gaussian window) behind
                      include/ngp_metrics.h; its sources live under csrc/metrics/.
+  libngp_meshdist.so -- the geometric distance between two meshes (surface samples, the nearest face through a uniform grid,
+                     the weighted statistics behind Chamfer, Hausdorff and F-score) behind include/ngp_meshdist.h; its sources
+                     live under csrc/meshdist/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -77,6 +80,11 @@ METRICS_SOURCES = [os.path.join("metrics", "metrics.hip")]
 METRICS_HEADERS = [os.path.join("..", "..", "include", "ngp_metrics.h")]
 # the filter taps, the index and the squared error are the plain f32 expressions of include/ngp_metrics.h, as tests/metrics_reference.py has them
 METRICS_CFLAGS = ["-ffp-contract=off"]
+MESHDIST_LIB = os.path.join(CSRC, "libngp_meshdist.so")
+MESHDIST_SOURCES = [os.path.join("meshdist", "meshdist.hip")]
+MESHDIST_HEADERS = [os.path.join("..", "..", "include", "ngp_meshdist.h")]
+# samples, the closest point of a triangle and the squared distance are the plain f32 expressions of include/ngp_meshdist.h, as tests/mesh_distance_reference.py has them
+MESHDIST_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -115,7 +123,8 @@ def build(force=False, verbose=False):
     smooth_objs, smooth_jobs = _plan(MESHSMOOTH_SOURCES, MESHSMOOTH_HEADERS, lambda src: MESHSMOOTH_CFLAGS, force)
     tex_objs, tex_jobs = _plan(MESHTEX_SOURCES, MESHTEX_HEADERS, lambda src: MESHTEX_CFLAGS, force)
     metrics_objs, metrics_jobs = _plan(METRICS_SOURCES, METRICS_HEADERS, lambda src: METRICS_CFLAGS, force)
-    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs
+    dist_objs, dist_jobs = _plan(MESHDIST_SOURCES, MESHDIST_HEADERS, lambda src: MESHDIST_CFLAGS, force)
+    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs + dist_jobs
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -124,7 +133,8 @@ def build(force=False, verbose=False):
     for lib, o, changed in ((LIB, objs, jobs), (MESH_LIB, mesh_objs, mesh_jobs), (MESHFILTER_LIB, filter_objs, filter_jobs),
                             (MESHCULL_LIB, cull_objs, cull_jobs), (MESHSIMPLIFY_LIB, simplify_objs, simplify_jobs),
                             (MESHTSDF_LIB, tsdf_objs, tsdf_jobs), (MESHSMOOTH_LIB, smooth_objs, smooth_jobs),
-                            (MESHTEX_LIB, tex_objs, tex_jobs), (METRICS_LIB, metrics_objs, metrics_jobs)):
+                            (MESHTEX_LIB, tex_objs, tex_jobs), (METRICS_LIB, metrics_objs, metrics_jobs),
+                            (MESHDIST_LIB, dist_objs, dist_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

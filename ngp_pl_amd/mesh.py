@@ -25,7 +25,11 @@
     img = render_textured(m, K, poses, (W, H))                     # (C, H, W, 3) f32: the textured mesh seen from the cameras
     m = extract_mesh(model, 512, keep_largest=1, simplify_voxels=2, smooth=10, texture=8)        # baked after the simplification, before the smoothing
     r = compare_renders(model, m, K, poses, (W, H))                # PSNR and SSIM of the textured mesh's renders against the field's (libngp_metrics.so)
+    p, w, i = sample_surface(m, spacing=voxel)                     # deterministic area samples: points, areas, face ids (libngp_meshdist.so)
+    d, i = closest_on_mesh(p, m2)                                  # distance to and index of the nearest face of m2, exactly the brute-force minimum
+    r = mesh_distance(m, m2, thresholds=(voxel,))                  # Chamfer, Hausdorff, precision / recall / F-score, per direction mean, rms, max
     save_ply("mesh.ply", m)
+    m = load_ply("mesh.ply", device="cuda")                        # what save_ply wrote, and nothing else
     save_obj("mesh.obj", m)                                        # mesh.obj + mesh.mtl + mesh.png (needs m.texture with an image)
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
@@ -33,6 +37,7 @@
                               [--simplify-voxels K] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
                               [--smooth-iterations N [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]]
                               [--texture-texels T [--score-cameras CAMS.npz [--score-out FILE.json]]]
+                              [--distance-to REF.ply [--distance-spacing S] [--distance-thresholds T1,T2,...] [--distance-out FILE.json]]
                               --out mesh.ply | mesh.obj
 
 Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
@@ -53,7 +58,8 @@ import zlib
 import numpy as np
 import torch
 
-from . import _lib, _mesh_lib, _meshcull_lib, _meshfilter_lib, _meshsimplify_lib, _meshsmooth_lib, _meshtex_lib, _meshtsdf_lib
+from . import (_lib, _mesh_lib, _meshcull_lib, _meshdist_lib, _meshfilter_lib, _meshsimplify_lib, _meshsmooth_lib, _meshtex_lib,
+               _meshtsdf_lib)
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -871,6 +877,272 @@ def compare_renders(model, textured_mesh, K, poses, img_wh, background=(1, 1, 1)
     return res
 
 
+def _mesh_extent(v, f):
+    """(7,) f64 on the device: the minimum and the maximum per axis of the finite vertices (+inf / -inf without any) and the mean
+    length of the edges of the faces whose indices are in range and whose vertices are finite (NaN without any).  No host sync."""
+    n_v, dev = v.shape[0], v.device
+    fin = torch.isfinite(v)
+    inf = torch.full((), float("inf"), dtype=torch.float32, device=dev)
+    lo = torch.where(fin, v, inf).amin(0) if n_v else inf.expand(3)
+    hi = torch.where(fin, v, -inf).amax(0) if n_v else (-inf).expand(3)
+    if n_v and f.shape[0]:
+        ok = ((f >= 0) & (f < n_v)).all(1)
+        t = v[f.clamp(0, n_v - 1).long()].double()                       # (F, 3, 3)
+        e = torch.stack([t[:, 1] - t[:, 0], t[:, 2] - t[:, 0], t[:, 2] - t[:, 1]], 1).norm(dim=2)
+        ok = ok & torch.isfinite(e).all(1)
+        mean = torch.where(ok[:, None], e, torch.zeros_like(e)).sum() / (3 * ok.sum())
+    else:
+        mean = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    return torch.cat([lo.double(), hi.double(), mean.view(1)])
+
+
+@dataclasses.dataclass
+class DistanceGrid:
+    origin: tuple               # 3 floats: the corner of cell (0, 0, 0)
+    cell: float                 # edge of a cell, as a float32 value
+    dims: tuple                 # (nx, ny, nz), each 1 .. 1024
+    workspace: object           # the library's workspace: the start of every cell's list
+    entries: object             # (E,) i32: the face lists
+    n_entries: int
+
+
+def _plan_grid(extent, cell):
+    """origin, cell and (nx, ny, nz) of the grid over the box `extent` = (lo3, hi3, mean edge) padded by half a cell: `cell` (None:
+    twice the mean edge) raised until every axis has at most 1024 cells, there are at most 2^30 in all, and the library's ratio of
+    cell to coordinate magnitude holds.  Host arithmetic only.  A target without finite vertices gets one cell at the origin."""
+    lo, hi, mean = extent[:3], extent[3:6], extent[6]
+    if not all(math.isfinite(x) for x in lo + hi):
+        lo, hi = [0.0] * 3, [0.0] * 3
+    if cell is None:
+        cell = 2.0 * mean if math.isfinite(mean) and mean > 0 else 1.0
+    magnitude = max(abs(x) for x in lo + hi)
+    lim = _meshdist_lib
+    cell = max(cell, 4.0 * lim.MIN_CELL_SLACKS * lim.SLACK_ULPS * 2.0 ** -23 * magnitude)
+    while True:
+        cell = C.c_float(cell).value
+        dims = [max(1, int(math.ceil((b - a) / cell + 1.0))) for a, b in zip(lo, hi)]
+        over = max(max(dims) / lim.MAX_AXIS, (dims[0] * dims[1] * dims[2] / lim.MAX_CELLS) ** (1.0 / 3.0))
+        if over <= 1.0:
+            break
+        cell *= 1.001 * over
+    origin = tuple(C.c_float(a - 0.5 * cell).value for a in lo)
+    return origin, cell, tuple(dims)
+
+
+def _build_grid(v, f, origin, cell, dims):
+    """ngp_meshdist_grid_count, one host read of the entry total, ngp_meshdist_grid_fill -> DistanceGrid."""
+    dev = v.device
+    ws_bytes = _meshdist_lib.lib().ngp_meshdist_grid_workspace_bytes(*dims)
+    if ws_bytes == 0:
+        raise ValueError("a grid of %r cells: every axis takes 1 .. 1024 cells and there are at most 2^30 in all" % (dims,))
+    o = _meshdist_lib.floats(origin)
+    with device_guard(dev):
+        s = stream()
+        ws = torch.empty(ws_bytes // 8 + 1, dtype=torch.int64, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        _meshdist_lib.call("ngp_meshdist_grid_count", ptr(v), ptr(f), v.shape[0], f.shape[0], o, cell, dims[0], dims[1], dims[2], ptr(ws),
+                           ws_bytes, ptr(total), s)
+        n_entries = int(total.item())
+        if n_entries > INT32_MAX:
+            raise ValueError("the grid has %d entries, more than INT32_MAX: use a larger cell" % n_entries)
+        entries = torch.empty(n_entries, dtype=torch.int32, device=dev)
+        _meshdist_lib.call("ngp_meshdist_grid_fill", ptr(v), ptr(f), v.shape[0], f.shape[0], o, cell, dims[0], dims[1], dims[2], ptr(ws),
+                           ws_bytes, n_entries, ptr(entries), s)
+    return DistanceGrid(tuple(origin), cell, tuple(dims), ws, entries, n_entries)
+
+
+def distance_grid(mesh, cell=None, origin=None, dims=None):
+    """The uniform grid closest_on_mesh searches, for reuse across calls: over the mesh's bounding box padded by half a cell, with
+    cells of twice the mean edge length (or `cell`), or exactly the grid given by `origin` (3 floats), `cell` and `dims`
+    (nx, ny, nz).  Whatever the grid, the query's result is the same bits.  Two host reads (the box, the entry total)."""
+    v, f, _ = _check_mesh(mesh)
+    if origin is None or dims is None:
+        if origin is not None or dims is not None:
+            raise ValueError("origin and dims go together, with cell")
+        origin, cell, dims = _plan_grid(_mesh_extent(v, f).tolist(), None if cell is None else _grid(cell, None)[0])
+    else:
+        cell = C.c_float(_grid(cell, origin)[0]).value
+        origin, dims = tuple(float(x) for x in np.asarray(origin, np.float64).reshape(-1)), tuple(int(n) for n in dims)
+    return _build_grid(v, f, origin, cell, dims)
+
+
+def _query(points, v, f, grid, max_dist, return_points, debug=False):
+    """ngp_meshdist_query -> d2 (N,) f32, face (N,) i32, closest (N, 3) f32 or None, debug (N, 2) i32 or None.  No host sync."""
+    n, dev = points.shape[0], points.device
+    d2 = torch.empty(n, dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    closest = torch.empty(n, 3, dtype=torch.float32, device=dev) if return_points else None
+    dbg = torch.empty(n, 2, dtype=torch.int32, device=dev) if debug else None
+    max_dist = float("inf") if max_dist is None else float(max_dist)
+    if not max_dist >= 0:
+        raise ValueError("max_dist must be >= 0 or None: %r" % (max_dist,))
+    with device_guard(dev):
+        _meshdist_lib.call("ngp_meshdist_query", ptr(points), n, ptr(v), ptr(f), v.shape[0], f.shape[0], _meshdist_lib.floats(grid.origin),
+                           grid.cell, grid.dims[0], grid.dims[1], grid.dims[2], max_dist, ptr(grid.workspace), grid.workspace.numel() * 8,
+                           ptr(grid.entries), grid.n_entries, ptr(d2), ptr(face), ptr(closest), ptr(dbg), stream())
+    return d2, face, closest, dbg
+
+
+def _check_points(points, v):
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError("points must be a (N, 3) float32 tensor")
+    _require_cuda(points, "points")
+    if points.device != v.device:
+        raise ValueError("points are on %s, the mesh on %s" % (points.device, v.device))
+    if points.shape[0] > INT32_MAX:
+        raise ValueError("more than INT32_MAX points")
+    return points.contiguous()
+
+
+def closest_on_mesh(points, mesh, cell=None, max_dist=None, return_points=False, squared=False, grid=None, return_debug=False):
+    """The nearest face of `mesh` for every point of points (N, 3) f32: (distance (N,) f32, face (N,) i32), and with
+    return_points=True also the closest point (N, 3) f32 on that face.  include/ngp_meshdist.h has the exact rule: the squared
+    distance to every usable face by the region test of Ericson's closest point of a triangle, in plain f32, and the minimum of
+    (its bits, the face index) over all faces -- the brute-force minimum, bit for bit, found through a uniform grid of cells of
+    `cell` (default: twice the mean edge length of the mesh, raised to the grid's limits where need be; the result does not depend
+    on it).  max_dist (None: no limit) turns a point whose nearest face is farther into a miss: distance +inf, face -1, point NaN;
+    so does a mesh without a usable face.  squared=True returns the squared distance the rule defines instead of its root;
+    grid=distance_grid(mesh) reuses a grid; return_debug=True appends (N, 2) i32: the shells visited and the faces evaluated per
+    point.  Two host reads to build the grid (the box, the entry total), none with grid=."""
+    v, f, _ = _check_mesh(mesh)
+    points = _check_points(points, v)
+    if grid is None:
+        grid = distance_grid(mesh, cell)
+    d2, face, closest, dbg = _query(points, v, f, grid, max_dist, return_points, return_debug)
+    out = (d2 if squared else d2.sqrt(), face) + ((closest,) if return_points else ()) + ((dbg,) if return_debug else ())
+    return out
+
+
+def _spacing(spacing):
+    spacing = C.c_float(float(spacing)).value
+    if not (math.isfinite(spacing) and spacing > 0):
+        raise ValueError("spacing must be finite and > 0 (as a float32): %r" % (spacing,))
+    return spacing
+
+
+def _sample_count(v, f, spacing):
+    """ngp_meshdist_sample_count -> the workspace, its size and the total (1,) i64 on the device (None for a mesh without faces)."""
+    n_f, dev = f.shape[0], v.device
+    if n_f == 0:
+        return None, 0, torch.zeros(1, dtype=torch.int64, device=dev)
+    ws_bytes = _meshdist_lib.lib().ngp_meshdist_sample_workspace_bytes(n_f)
+    with device_guard(dev):
+        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        _meshdist_lib.call("ngp_meshdist_sample_count", ptr(v), ptr(f), v.shape[0], n_f, spacing, ptr(ws), ws_bytes, ptr(total), stream())
+    return ws, ws_bytes, total
+
+
+def _sample_emit(v, f, spacing, ws, ws_bytes, n):
+    dev = v.device
+    if n > INT32_MAX:
+        raise ValueError("%d samples, more than INT32_MAX: use a larger spacing" % n)
+    points = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    weights = torch.empty(n, dtype=torch.float32, device=dev)
+    ids = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        with device_guard(dev):
+            _meshdist_lib.call("ngp_meshdist_sample_emit", ptr(v), ptr(f), v.shape[0], f.shape[0], spacing, ptr(ws), ws_bytes, n, ptr(points),
+                               ptr(weights), ptr(ids), stream())
+    return points, weights, ids
+
+
+def sample_surface(mesh, spacing):
+    """Deterministic samples of the mesh's surface: (points (S, 3) f32, weights (S,) f32, face_ids (S,) i32).  A face with finite
+    vertices and indices in range is cut into k x k similar triangles, k = ceil(longest edge / spacing) clamped to 1 .. 64, and
+    gives their centroids, each weighted by its sub-triangle's area; other faces give nothing.  Samples come in face order.  The
+    exact rule is in include/ngp_meshdist.h.  One host read (the number of samples)."""
+    spacing = _spacing(spacing)
+    v, f, _ = _check_mesh(mesh)
+    ws, ws_bytes, total = _sample_count(v, f, spacing)
+    return _sample_emit(v, f, spacing, ws, ws_bytes, int(total.item()))
+
+
+def _stats(d2, face, weights, thresholds):
+    """ngp_meshdist_stats -> (14,) f64 on the device; zeros for no elements.  No host sync."""
+    n, dev = d2.shape[0], d2.device
+    out = torch.zeros(_meshdist_lib.STATS_OUTPUTS, dtype=torch.float64, device=dev)
+    if n:
+        ws_bytes = _meshdist_lib.lib().ngp_meshdist_stats_workspace_bytes(n)
+        with device_guard(dev):
+            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+            _meshdist_lib.call("ngp_meshdist_stats", ptr(d2), ptr(face), ptr(weights), n, _meshdist_lib.floats(thresholds), len(thresholds),
+                               ptr(ws), ws_bytes, ptr(out), stream())
+    return out
+
+
+def distance_statistics(d2, face, weights, thresholds=()):
+    """The sums of include/ngp_meshdist.h rule 4 over squared distances d2 (N,) f32, faces (N,) i32 (-1: a miss) and weights (N,)
+    f32, as a (14,) f64 device tensor: sum w, sum w d, sum w d^2, max d, the weight and the number of the misses, and per
+    threshold (at most 8) the weight within it.  The same inputs give the same bits.  No host sync."""
+    thresholds = _thresholds(thresholds)
+    for name, a, dt in (("d2", d2, torch.float32), ("face", face, torch.int32), ("weights", weights, torch.float32)):
+        if not isinstance(a, torch.Tensor) or a.dim() != 1 or a.dtype != dt or a.shape[0] != d2.shape[0]:
+            raise ValueError("%s must be a (N,) %s tensor" % (name, dt))
+        _require_cuda(a, name)
+    return _stats(d2.contiguous(), face.contiguous(), weights.contiguous(), thresholds)
+
+
+def _thresholds(thresholds):
+    thresholds = [C.c_float(float(t)).value for t in thresholds]
+    if len(thresholds) > _meshdist_lib.MAX_THRESHOLDS or any(not t >= 0 for t in thresholds):
+        raise ValueError("thresholds: at most %d distances, each >= 0: %r" % (_meshdist_lib.MAX_THRESHOLDS, thresholds))
+    return thresholds
+
+
+def mesh_distance(a, b, spacing=None, thresholds=(), max_dist=None, per_vertex=False):
+    """The geometric distance between the surfaces of two meshes on one device.  Both are sampled (sample_surface with `spacing`;
+    None: the smaller of the two meshes' mean edge lengths), every sample of one is sent to the nearest face of the other
+    (closest_on_mesh, with max_dist), and the area-weighted statistics come back as a dict:
+      a_to_b, b_to_a   dict(area=the sampled area, samples=, mean=, rms=, max= of the distance over the samples that found a face,
+                       miss_share=the share of the area whose sample found none within max_dist,
+                       within=[the share of the area within each threshold])
+      chamfer          a_to_b.mean + b_to_a.mean            hausdorff    max(a_to_b.max, b_to_a.max)
+      thresholds, precision (= a_to_b.within), recall (= b_to_a.within), fscore (2 P R / (P + R); 0 where both vanish)
+      spacing          the spacing used
+    per_vertex=True adds vertex_distance (Va,) f32 on the device: the distance of every vertex of `a` to `b`, e.g. to colour an
+    error map for save_ply.  A direction without samples reports NaN for its mean, rms and shares.  Host reads: one for the
+    boxes and the sample counts (one more before it when spacing is None), one entry total per grid, one at the end."""
+    thresholds = _thresholds(thresholds)
+    (va, fa, _), (vb, fb, _) = _check_mesh(a), _check_mesh(b)
+    if va.device != vb.device:
+        raise ValueError("the meshes are on %s and %s" % (va.device, vb.device))
+    extents = torch.stack([_mesh_extent(va, fa), _mesh_extent(vb, fb)])
+    host = None
+    if spacing is None:
+        host = extents.tolist()
+        means = [e[6] for e in host if math.isfinite(e[6]) and e[6] > 0]
+        spacing = min(means) if means else 1.0
+    spacing = _spacing(spacing)
+    counted = [_sample_count(v, f, spacing) for v, f in ((va, fa), (vb, fb))]
+    setup = torch.cat([extents.view(-1), counted[0][2].double(), counted[1][2].double()]).tolist()
+    n_samples = [int(setup[14]), int(setup[15])]
+    samples = [_sample_emit(v, f, spacing, c[0], c[1], n) for (v, f), c, n in zip(((va, fa), (vb, fb)), counted, n_samples)]
+    grids = [_build_grid(v, f, *_plan_grid(setup[7 * k:7 * k + 7], None)) for k, (v, f) in enumerate(((va, fa), (vb, fb)))]
+    rows = []
+    for src, dst in ((0, 1), (1, 0)):
+        v, f = (va, fa) if dst == 0 else (vb, fb)
+        d2, face, _, _ = _query(samples[src][0], v, f, grids[dst], max_dist, False)
+        rows.append(_stats(d2, face, samples[src][1], thresholds))
+    vertex_distance = None
+    if per_vertex:
+        vertex_distance = _query(va, vb, fb, grids[1], max_dist, False)[0].sqrt()
+    host = torch.stack(rows).tolist()                                  # the one read of the results
+    ratio = lambda x, y: x / y if y else float("nan")
+    res = {}
+    for name, r, n in zip(("a_to_b", "b_to_a"), host, n_samples):
+        area = r[0] + r[4]
+        res[name] = dict(area=area, samples=n, mean=ratio(r[1], r[0]), rms=math.sqrt(ratio(r[2], r[0])) if r[0] else float("nan"),
+                         max=r[3], miss_share=ratio(r[4], area), within=[ratio(x, area) for x in r[6:6 + len(thresholds)]])
+    p, r = res["a_to_b"]["within"], res["b_to_a"]["within"]
+    res.update(chamfer=res["a_to_b"]["mean"] + res["b_to_a"]["mean"], hausdorff=max(res["a_to_b"]["max"], res["b_to_a"]["max"]),
+               thresholds=thresholds, precision=p, recall=r, fscore=[2 * x * y / (x + y) if x + y > 0 else 0.0 for x, y in zip(p, r)],
+               spacing=spacing)
+    if per_vertex:
+        res["vertex_distance"] = vertex_distance
+    return res
+
+
 def _texture_options(texture):
     """extract_mesh's `texture`: None, an int (texels) or dict(texels=) -> None or the checked texels."""
     if texture is None:
@@ -1017,6 +1289,59 @@ def save_ply(path, m):
         out.write(frec.tobytes())
 
 
+_PLY_VERTEX = (["x", "y", "z"], ["nx", "ny", "nz"], ["red", "green", "blue"])
+
+
+def load_ply(path, device=None):
+    """Reads the binary little-endian PLY that save_ply writes -> Mesh (tensors on `device`; None: the CPU): vertices x y z (float),
+    optionally nx ny nz (float), optionally red green blue (uchar, returned as float32 / 255), and faces as
+    `list uchar int vertex_indices`, all triangles.  Anything else -- another format, other elements, properties or types, faces
+    that are not triangles, a short or a long file -- is refused with a ValueError that says what was found."""
+    with open(path, "rb") as src:
+        blob = src.read()
+    end = blob.find(b"end_header\n")
+    if not blob.startswith(b"ply\n") or end < 0:
+        raise ValueError("%s: not a PLY file (no 'ply' / 'end_header' lines)" % path)
+    lines = blob[:end].decode("ascii", "replace").split("\n")[1:]
+    lines = [l for l in lines if l and not l.startswith("comment")]
+    if not lines or lines[0] != "format binary_little_endian 1.0":
+        raise ValueError("%s: only 'format binary_little_endian 1.0' is read, found %r" % (path, lines[0] if lines else ""))
+    elements = []
+    for l in lines[1:]:
+        w = l.split()
+        if w[0] == "element" and len(w) == 3 and w[2].isdigit():
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == "property" and elements:
+            elements[-1][2].append(tuple(w[1:]))
+        else:
+            raise ValueError("%s: header line %r is not understood" % (path, l))
+    if [e[0] for e in elements] != ["vertex", "face"]:
+        raise ValueError("%s: the elements must be vertex then face, found %r" % (path, [e[0] for e in elements]))
+    (_, n_v, vprops), (_, n_f, fprops) = elements
+    names = [p[-1] for p in vprops]
+    has_n, has_c = "nx" in names, "red" in names
+    want = _PLY_VERTEX[0] + (_PLY_VERTEX[1] if has_n else []) + (_PLY_VERTEX[2] if has_c else [])
+    types = ["float"] * (6 if has_n else 3) + (["uchar"] * 3 if has_c else [])
+    if names != want or [p[0] for p in vprops] != types or any(len(p) != 2 for p in vprops):
+        raise ValueError("%s: vertex properties must be float x y z [float nx ny nz] [uchar red green blue], found %r" % (path, vprops))
+    if fprops != [("list", "uchar", "int", "vertex_indices")]:
+        raise ValueError("%s: the face property must be 'list uchar int vertex_indices', found %r" % (path, fprops))
+    vdt = np.dtype([(n, "<f4" if t == "float" else "u1") for n, t in zip(names, types)])
+    fdt = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+    body = end + len(b"end_header\n")
+    if len(blob) - body != n_v * vdt.itemsize + n_f * fdt.itemsize:
+        raise ValueError("%s: %d bytes of data, %d vertices and %d triangles take %d" % (path, len(blob) - body, n_v, n_f,
+                                                                                         n_v * vdt.itemsize + n_f * fdt.itemsize))
+    rec = np.frombuffer(blob, vdt, n_v, body)
+    frec = np.frombuffer(blob, fdt, n_f, body + n_v * vdt.itemsize)
+    if n_f and (frec["n"] != 3).any():
+        raise ValueError("%s: a face that is not a triangle" % path)
+    put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device if device is not None else "cpu")
+    cols = lambda ns: np.stack([rec[n] for n in ns], 1).astype(np.float32).reshape(-1, 3)
+    return Mesh(put(cols(_PLY_VERTEX[0])), put(frec["v"].astype(np.int32).reshape(-1, 3)), put(cols(_PLY_VERTEX[1])) if has_n else None,
+                put(cols(_PLY_VERTEX[2]) / np.float32(255.0)) if has_c else None)
+
+
 def _png(image):
     """The bytes of an 8-bit RGB PNG of image (H, W, 3) u8: filter 0 on every row, one IDAT chunk."""
     h, w, _ = image.shape
@@ -1092,6 +1417,12 @@ def main(argv=None):
                     help="score the textured mesh against the field's own renders from these cameras (PSNR, SSIM; compare_renders) and "
                          "print the record as one JSON line: an .npz as --cull-cameras takes; needs --texture-texels")
     ap.add_argument("--score-out", default=None, metavar="FILE.json", help="also write the record of --score-cameras to this file")
+    ap.add_argument("--distance-to", default=None, metavar="REF.ply",
+                    help="measure the exported mesh against this mesh (a PLY as this tool writes it; mesh_distance) and print the record as "
+                         "one JSON line: Chamfer and Hausdorff distance, precision, recall and F-score, per direction mean, rms and max")
+    ap.add_argument("--distance-spacing", type=float, default=None, metavar="S", help="sample spacing (default: the smaller mean edge length)")
+    ap.add_argument("--distance-thresholds", default=None, metavar="T1,T2,...", help="up to 8 distances for precision, recall and F-score")
+    ap.add_argument("--distance-out", default=None, metavar="FILE.json", help="also write the record of --distance-to to this file")
     ap.add_argument("--out", required=True, help="output .ply, or .obj (written with its .mtl and .png; needs --texture-texels)")
     a = ap.parse_args(argv)
     if len(a.resolution) not in (1, 3):
@@ -1118,6 +1449,16 @@ def main(argv=None):
         ap.error("--score-cameras needs --texture-texels: the score is of the textured mesh")
     if a.score_out is not None and a.score_cameras is None:
         ap.error("--score-out needs --score-cameras")
+    distance_thresholds = ()
+    if a.distance_to is None and (a.distance_spacing is not None or a.distance_thresholds is not None or a.distance_out is not None):
+        ap.error("--distance-spacing, --distance-thresholds and --distance-out need --distance-to")
+    if a.distance_spacing is not None and not (math.isfinite(a.distance_spacing) and a.distance_spacing > 0):
+        ap.error("--distance-spacing takes S > 0")
+    if a.distance_thresholds is not None:
+        try:
+            distance_thresholds = _thresholds(a.distance_thresholds.split(","))
+        except ValueError:
+            ap.error("--distance-thresholds takes up to 8 comma-separated distances >= 0")
     from .networks import NGP
     from .utils import load_ckpt
     model = NGP(scale=a.scale, level_table=a.level_table).cuda()
@@ -1164,6 +1505,16 @@ def main(argv=None):
         text = json.dumps(record)
         if a.score_out is not None:
             with open(a.score_out, "w") as f:
+                f.write(text + "\n")
+        print(text)
+    if a.distance_to is not None:
+        import json
+        ref = load_ply(a.distance_to, device=m.vertices.device)
+        record = mesh_distance(Mesh(m.vertices, m.faces), Mesh(ref.vertices, ref.faces), spacing=a.distance_spacing,
+                               thresholds=distance_thresholds)
+        text = json.dumps(record)
+        if a.distance_out is not None:
+            with open(a.distance_out, "w") as f:
                 f.write(text + "\n")
         print(text)
     return 0
