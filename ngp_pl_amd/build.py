@@ -22,6 +22,8 @@
   libngp_meshdist.so -- the geometric distance between two meshes (surface samples, the nearest face through a uniform grid,
                      the weighted statistics behind Chamfer, Hausdorff and F-score) behind include/ngp_meshdist.h; its sources
                      live under csrc/meshdist/.
+  libngp_meshquadric.so -- quadric placement of the vertices of a vertex clustering (exact int64 quadric sums per cluster, a
+                     regularised 3x3 solve in f64) behind include/ngp_meshquadric.h; its sources live under csrc/meshquadric/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -85,6 +87,11 @@ MESHDIST_SOURCES = [os.path.join("meshdist", "meshdist.hip")]
 MESHDIST_HEADERS = [os.path.join("..", "..", "include", "ngp_meshdist.h")]
 # samples, the closest point of a triangle and the squared distance are the plain f32 expressions of include/ngp_meshdist.h, as tests/mesh_distance_reference.py has them
 MESHDIST_CFLAGS = ["-ffp-contract=off"]
+MESHQUADRIC_LIB = os.path.join(CSRC, "libngp_meshquadric.so")
+MESHQUADRIC_SOURCES = [os.path.join("meshquadric", "meshquadric.hip")]
+MESHQUADRIC_HEADERS = [os.path.join("..", "..", "include", "ngp_meshquadric.h")]
+# cells, planes, weights, the rounding to int64 and the f64 solve are the plain expressions of include/ngp_meshquadric.h, as tests/mesh_quadric_reference.py has them
+MESHQUADRIC_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -124,7 +131,9 @@ def build(force=False, verbose=False):
     tex_objs, tex_jobs = _plan(MESHTEX_SOURCES, MESHTEX_HEADERS, lambda src: MESHTEX_CFLAGS, force)
     metrics_objs, metrics_jobs = _plan(METRICS_SOURCES, METRICS_HEADERS, lambda src: METRICS_CFLAGS, force)
     dist_objs, dist_jobs = _plan(MESHDIST_SOURCES, MESHDIST_HEADERS, lambda src: MESHDIST_CFLAGS, force)
-    todo = jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs + dist_jobs
+    quadric_objs, quadric_jobs = _plan(MESHQUADRIC_SOURCES, MESHQUADRIC_HEADERS, lambda src: MESHQUADRIC_CFLAGS, force)
+    todo = (jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs + dist_jobs
+            + quadric_jobs)
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -134,7 +143,7 @@ def build(force=False, verbose=False):
                             (MESHCULL_LIB, cull_objs, cull_jobs), (MESHSIMPLIFY_LIB, simplify_objs, simplify_jobs),
                             (MESHTSDF_LIB, tsdf_objs, tsdf_jobs), (MESHSMOOTH_LIB, smooth_objs, smooth_jobs),
                             (MESHTEX_LIB, tex_objs, tex_jobs), (METRICS_LIB, metrics_objs, metrics_jobs),
-                            (MESHDIST_LIB, dist_objs, dist_jobs)):
+                            (MESHDIST_LIB, dist_objs, dist_jobs), (MESHQUADRIC_LIB, quadric_objs, quadric_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

@@ -11,6 +11,8 @@
     m = extract_mesh(model, 512, keep_largest=1, cull=dict(K=K, poses=poses, img_wh=(W, H)))     # the same, after the filter
     l = vertex_clusters(m, cell=0.004)                             # (V,) i32: smallest vertex index in the vertex's grid cell
     m = simplify_clusters(m, cell=0.004)                           # one vertex per occupied cell (libngp_meshsimplify.so)
+    p, s, l = cluster_placement(m, cell=0.004)                     # per cluster: the point nearest the planes of its faces (libngp_meshquadric.so)
+    m = simplify_clusters(m, cell=0.004, placement="quadric")      # the same faces, the vertices there instead of at the mean: creases stay sharp
     m = extract_mesh(model, 512, keep_largest=1, simplify_voxels=2, colors=True)     # cells of 2 voxels, after filter and cull
     d = render_depths(model, K, poses, (W, H))                     # (C, H, W) f32: camera-space z of what each pixel sees, +inf for nothing
     vol = tsdf_volume(512, (lo3, hi3), K, poses, (W, H), d, trunc=4 * voxel)   # depth maps fused into a TSDF (libngp_meshtsdf.so); level 0
@@ -34,7 +36,7 @@
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
                               [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]]
-                              [--simplify-voxels K] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
+                              [--simplify-voxels K [--simplify-placement {mean,quadric}]] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
                               [--smooth-iterations N [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]]
                               [--texture-texels T [--score-cameras CAMS.npz [--score-out FILE.json]]]
                               [--distance-to REF.ply [--distance-spacing S] [--distance-thresholds T1,T2,...] [--distance-out FILE.json]]
@@ -58,8 +60,8 @@ import zlib
 import numpy as np
 import torch
 
-from . import (_lib, _mesh_lib, _meshcull_lib, _meshdist_lib, _meshfilter_lib, _meshsimplify_lib, _meshsmooth_lib, _meshtex_lib,
-               _meshtsdf_lib)
+from . import (_lib, _mesh_lib, _meshcull_lib, _meshdist_lib, _meshfilter_lib, _meshquadric_lib, _meshsimplify_lib, _meshsmooth_lib,
+               _meshtex_lib, _meshtsdf_lib)
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -521,16 +523,90 @@ def _simplify(v, f, extra, cell, origin):
     return Mesh(out[0], faces, out[1], out[2]), label, (n_ov, n_of, n_clusters)
 
 
-def simplify_clusters(mesh, cell, origin=None):
+PLACEMENTS = ("mean", "quadric")
+
+
+def _placement(placement, what="placement"):
+    if not isinstance(placement, str) or placement not in PLACEMENTS:
+        raise ValueError("%s must be one of %r: %r" % (what, PLACEMENTS, placement))
+    return placement
+
+
+def _place(v, f, label, cell, o):
+    """ngp_meshquadric_accumulate + ngp_meshquadric_place for the labels of _cluster on the same grid -> positions (V, 3) f32
+    (written at leaders only), state (V,) u8, totals (3,) i64 on the device and the workspace.  No host sync."""
+    n_v, n_f, dev = v.shape[0], f.shape[0], v.device
+    ws_bytes = _meshquadric_lib.lib().ngp_meshquadric_workspace_bytes(n_v, n_f)
+    with device_guard(dev):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        positions = torch.zeros(n_v, 3, dtype=torch.float32, device=dev)
+        state = torch.empty(n_v, dtype=torch.uint8, device=dev)
+        totals = torch.empty(3, dtype=torch.int64, device=dev)
+        _meshquadric_lib.call("ngp_meshquadric_accumulate", ptr(v), ptr(f), ptr(label), n_v, n_f, ptr(o), cell, ptr(ws), ws_bytes, stream())
+        _meshquadric_lib.call("ngp_meshquadric_place", ptr(v), ptr(label), n_v, ptr(o), cell, ptr(ws), ws_bytes, ptr(positions), ptr(state),
+                              ptr(totals), stream())
+    return positions, state, totals, (ws, ws_bytes)
+
+
+def cluster_placement(mesh, cell, origin=None):
+    """(positions (V, 3) f32, state (V,) u8, label (V,) i32) of the clusters of vertex_clusters(mesh, cell, origin): at every
+    cluster's leader (the vertex whose index is the label) the position that minimises the summed squared distances to the planes of
+    the faces that touch the cluster, each weighted by the face's area (Lindstrom's quadric placement for vertex clustering;
+    libngp_meshquadric.so, include/ngp_meshquadric.h has the exact rule), and zeros elsewhere.  state: 0 not a leader, 1 QUADRIC,
+    2 MEAN_NO_FACES (no face with an area touches the cluster), 3 MEAN_OUTSIDE (the minimiser lies more than half a cell beyond the
+    cluster's cell, as for two nearly parallel sheets); in states 2 and 3 the position is the members' mean, bit for bit the one
+    simplify_clusters gives.  The sums are exact integers: the result is the same on every run and for any order of the faces.
+    No host sync."""
+    cell, origin = _grid(cell, origin)
+    v, f, _ = _check_mesh(mesh)
+    if v.shape[0] == 0:
+        dev = v.device
+        return (torch.empty(0, 3, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.uint8, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev))
+    label, _, _, o = _cluster(v, (None, None), cell, origin, 0)
+    positions, state, _, _ = _place(v, f, label, cell, o)
+    return positions, state, label
+
+
+def _used_labels(f, label, n_v):
+    """(V,) bool: the clusters a surviving face references, i.e. the output vertices of _simplify in their order.  Duplicate faces
+    reference the clusters of the one that is kept, so the duplicate table is not needed.  No host sync."""
+    valid = ((f >= 0) & (f < n_v)).all(1)
+    lab = label[f.clamp(0, n_v - 1).long()]
+    keep = valid & (lab >= 0).all(1) & (lab[:, 0] != lab[:, 1]) & (lab[:, 1] != lab[:, 2]) & (lab[:, 0] != lab[:, 2])
+    used = torch.zeros(n_v + 1, dtype=torch.bool, device=f.device)             # row n_v takes the faces that do not survive
+    used[torch.where(keep[:, None], lab, n_v).long().reshape(-1)] = True
+    return used[:n_v]
+
+
+def simplify_clusters(mesh, cell, origin=None, placement="mean"):
     """The mesh with every cluster of vertex_clusters merged into one vertex: its position is the mean of the members' positions,
     its normal the normalised sum of theirs, its colour their mean (None stays None), each summed exactly in 2^-20 fixed point so
     that the result is the same on every run.  Faces that lose a corner to a merge go, and of the faces that end on the same three
     clusters the first stays, in its own orientation; vertices come back in the order of their clusters' smallest members, faces in
     their own order.  Nothing kept gives (0, 3) tensors.  Clustering can pinch a thin wall: the result need not be manifold.
-    Mesh-only: the field is not read.  One host sync for the output sizes."""
+    Mesh-only: the field is not read.  One host sync for the output sizes.
+    placement="quadric" puts every vertex at cluster_placement's position instead of the mean, which keeps creases and corners
+    sharp where the mean rounds them off by a fraction of a cell; faces, vertex order, normals and colours are exactly those of
+    "mean".  It adds two library calls and device-side indexing, and no host sync beyond the one above."""
+    placement = _placement(placement)
     cell, origin = _grid(cell, origin)
     v, f, extra = _check_mesh(mesh)
-    return _simplify(v, f, extra, cell, origin)[0]
+    if placement == "mean" or v.shape[0] == 0:
+        return _simplify(v, f, extra, cell, origin)[0]
+    n_v, dev = v.shape[0], v.device
+    o = (v.amin(0) if origin is None else torch.as_tensor(origin, dtype=torch.float32).reshape(3).to(dev)).contiguous()
+    m, label, (n_ov, _, _) = _simplify(v, f, extra, cell, o)
+    if n_ov == 0:
+        return m
+    positions = _place(v, f, label, cell, o)[0]
+    used = _used_labels(f, label, n_v)
+    # output vertex i is the i-th used label: scatter by rank, the unused rows into a spare last row
+    rank = torch.cumsum(used, 0) - 1
+    out = torch.empty(n_ov + 1, 3, dtype=torch.float32, device=dev)
+    out[torch.where(used, rank, n_ov)] = positions
+    m.vertices = out[:n_ov]
+    return m
 
 
 @dataclasses.dataclass
@@ -1179,7 +1255,7 @@ def _tsdf(model, resolution, lo, hi, K, poses, img_wh, trunc_voxels=4.0, min_opa
 
 
 def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None, simplify_voxels=None, tsdf=None,
-             smooth=None, texture=None):
+             smooth=None, texture=None, simplify_placement="mean"):
     """extract_mesh (with `texture`: baked after the simplification and the colours, before the smoothing), (components found, components kept) when a filter option is set (else None), the number of faces the cull
     dropped when `cull` is set (else None), (V0, V1, F0, F1) around the simplification when simplify_voxels is set (else None), and
     (pairs, the topology's totals (4,) i64 on the device or None) when `smooth` is set (else None)."""
@@ -1187,6 +1263,9 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
     texture = _texture_options(texture)
     if simplify_voxels is not None and not (math.isfinite(float(simplify_voxels)) and float(simplify_voxels) > 0):
         raise ValueError("simplify_voxels must be a finite number > 0: %r" % (simplify_voxels,))
+    simplify_placement = _placement(simplify_placement, "simplify_placement")
+    if simplify_placement != "mean" and simplify_voxels is None:
+        raise ValueError("simplify_placement=%r needs simplify_voxels: there is nothing to place" % (simplify_placement,))
     lo, hi = _bounds(model, bounds)
     if tsdf is None:
         vol = density_volume(model, resolution, (lo, hi))
@@ -1214,7 +1293,7 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
     if simplify_voxels is not None:
         cell = float(simplify_voxels) * max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution)))
         before = (m.vertices.shape[0], m.faces.shape[0])
-        m = simplify_clusters(m, cell, origin=lo)
+        m = simplify_clusters(m, cell, origin=lo, placement=simplify_placement)
         simplified = (before[0], m.vertices.shape[0], before[1], m.faces.shape[0])
     if colors:
         m.colors = vertex_colors(model, m.vertices, m.normals)
@@ -1233,11 +1312,12 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
 
 
 def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None, cull=None,
-                 simplify_voxels=None, tsdf=None, smooth=None, texture=None):
+                 simplify_voxels=None, tsdf=None, smooth=None, texture=None, simplify_placement="mean"):
     """density_volume + marching_cubes in the model's world coordinates; keep_largest / min_component_faces filter the components
     (filter_components); cull=dict(K=, poses=, img_wh=, min_views=1, bias=None) then drops the faces none of those cameras sees
     (cull_invisible; bias=None is twice the largest lattice spacing); simplify_voxels=K then merges the vertices of every grid
-    cell of K times the largest lattice spacing, the grid starting at the bounds' lower corner (simplify_clusters); colors=True adds
+    cell of K times the largest lattice spacing, the grid starting at the bounds' lower corner (simplify_clusters), each merged vertex
+    at the members' mean or, with simplify_placement="quadric", at the point nearest the planes of the cluster's faces; colors=True adds
     vertex_colors, evaluated after all three on the vertices that are left, along minus their (averaged) normals.
     tsdf=dict(K=, poses=, img_wh=, trunc_voxels=4.0, min_opacity=0.5, depths=None) replaces the first stage: instead of the density
     thresholded at `threshold` (which is then not used), the volume is tsdf_volume of the depth maps those cameras render
@@ -1252,7 +1332,7 @@ def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=Fals
     sampled on the surface the field defines and along minus the gradient normals, the rule `colors` follows.  Without it
     mesh.texture is None and everything else is the same bits."""
     return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels, tsdf, smooth,
-                    texture)[0]
+                    texture, simplify_placement)[0]
 
 
 def _np(a):
@@ -1401,6 +1481,9 @@ def main(argv=None):
     ap.add_argument("--cull-bias", type=float, default=None, metavar="B", help="depth slack in world units (default: two voxels)")
     ap.add_argument("--simplify-voxels", type=float, default=None, metavar="K",
                     help="merge the vertices of every grid cell of K voxels (vertex clustering), after the filter and the cull")
+    ap.add_argument("--simplify-placement", default=None, choices=PLACEMENTS,
+                    help="where a merged vertex goes: the mean of its cell's vertices (the default), or the point nearest the planes of "
+                         "the faces around them (quadric), which keeps creases sharp; needs --simplify-voxels")
     ap.add_argument("--tsdf-cameras", default=None, metavar="FILE.npz",
                     help="mesh the TSDF fusion of the depth maps these cameras render instead of the thresholded density: an .npz as "
                          "--cull-cameras takes (--threshold is then not used)")
@@ -1431,6 +1514,8 @@ def main(argv=None):
         ap.error("--keep-largest takes K >= 0")
     if a.simplify_voxels is not None and not (math.isfinite(a.simplify_voxels) and a.simplify_voxels > 0):
         ap.error("--simplify-voxels takes K > 0")
+    if a.simplify_placement is not None and a.simplify_voxels is None:
+        ap.error("--simplify-placement needs --simplify-voxels")
     if not (math.isfinite(a.tsdf_trunc_voxels) and a.tsdf_trunc_voxels > 0):
         ap.error("--tsdf-trunc-voxels takes T > 0")
     if a.smooth_iterations is not None and a.smooth_iterations < 0:
@@ -1478,7 +1563,7 @@ def main(argv=None):
     if a.smooth_iterations is not None:
         smooth = dict(iterations=a.smooth_iterations, lam=a.smooth_lambda, mu=a.smooth_mu, pin_boundary=not a.smooth_free_boundary)
     m, found, culled, simplified, smoothed = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull,
-                                                      a.simplify_voxels, tsdf, smooth, a.texture_texels)
+                                                      a.simplify_voxels, tsdf, smooth, a.texture_texels, a.simplify_placement or "mean")
     if obj:
         save_obj(a.out, m)
     else:
