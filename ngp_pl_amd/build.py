@@ -24,6 +24,9 @@
                      live under csrc/meshdist/.
   libngp_meshquadric.so -- quadric placement of the vertices of a vertex clustering (exact int64 quadric sums per cluster, a
                      regularised 3x3 solve in f64) behind include/ngp_meshquadric.h; its sources live under csrc/meshquadric/.
+  libngp_meshdecimate.so -- decimation of a mesh to a face budget or an error bound by rounds of independent half-edge collapses
+                     (integer plane-distance costs, claim words, the shared compaction) behind include/ngp_meshdecimate.h; its
+                     sources live under csrc/meshdecimate/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -92,6 +95,11 @@ MESHQUADRIC_SOURCES = [os.path.join("meshquadric", "meshquadric.hip")]
 MESHQUADRIC_HEADERS = [os.path.join("..", "..", "include", "ngp_meshquadric.h")]
 # cells, planes, weights, the rounding to int64 and the f64 solve are the plain expressions of include/ngp_meshquadric.h, as tests/mesh_quadric_reference.py has them
 MESHQUADRIC_CFLAGS = ["-ffp-contract=off"]
+MESHDECIMATE_LIB = os.path.join(CSRC, "libngp_meshdecimate.so")
+MESHDECIMATE_SOURCES = [os.path.join("meshdecimate", "meshdecimate.hip")]
+MESHDECIMATE_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshdecimate.h")]
+# cross products, the flip and error tests and the rounding of the costs to int64 are the plain f64 expressions of include/ngp_meshdecimate.h, as tests/mesh_decimate_reference.py has them
+MESHDECIMATE_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -132,8 +140,9 @@ def build(force=False, verbose=False):
     metrics_objs, metrics_jobs = _plan(METRICS_SOURCES, METRICS_HEADERS, lambda src: METRICS_CFLAGS, force)
     dist_objs, dist_jobs = _plan(MESHDIST_SOURCES, MESHDIST_HEADERS, lambda src: MESHDIST_CFLAGS, force)
     quadric_objs, quadric_jobs = _plan(MESHQUADRIC_SOURCES, MESHQUADRIC_HEADERS, lambda src: MESHQUADRIC_CFLAGS, force)
+    decimate_objs, decimate_jobs = _plan(MESHDECIMATE_SOURCES, MESHDECIMATE_HEADERS, lambda src: MESHDECIMATE_CFLAGS, force)
     todo = (jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs + dist_jobs
-            + quadric_jobs)
+            + quadric_jobs + decimate_jobs)
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -143,7 +152,8 @@ def build(force=False, verbose=False):
                             (MESHCULL_LIB, cull_objs, cull_jobs), (MESHSIMPLIFY_LIB, simplify_objs, simplify_jobs),
                             (MESHTSDF_LIB, tsdf_objs, tsdf_jobs), (MESHSMOOTH_LIB, smooth_objs, smooth_jobs),
                             (MESHTEX_LIB, tex_objs, tex_jobs), (METRICS_LIB, metrics_objs, metrics_jobs),
-                            (MESHDIST_LIB, dist_objs, dist_jobs), (MESHQUADRIC_LIB, quadric_objs, quadric_jobs)):
+                            (MESHDIST_LIB, dist_objs, dist_jobs), (MESHQUADRIC_LIB, quadric_objs, quadric_jobs),
+                            (MESHDECIMATE_LIB, decimate_objs, decimate_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

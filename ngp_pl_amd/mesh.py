@@ -14,6 +14,9 @@
     p, s, l = cluster_placement(m, cell=0.004)                     # per cluster: the point nearest the planes of its faces (libngp_meshquadric.so)
     m = simplify_clusters(m, cell=0.004, placement="quadric")      # the same faces, the vertices there instead of at the mean: creases stay sharp
     m = extract_mesh(model, 512, keep_largest=1, simplify_voxels=2, colors=True)     # cells of 2 voxels, after filter and cull
+    m = decimate(m, cell=voxel, target_faces=100000)               # edge collapses down to a face budget (libngp_meshdecimate.so)
+    m = decimate(m, cell=voxel, max_error=0.5 * voxel)             # or while no vertex leaves its faces' planes by more than that
+    m = extract_mesh(model, 512, keep_largest=1, decimate=100000, colors=True)       # after the clustering, before the colours
     d = render_depths(model, K, poses, (W, H))                     # (C, H, W) f32: camera-space z of what each pixel sees, +inf for nothing
     vol = tsdf_volume(512, (lo3, hi3), K, poses, (W, H), d, trunc=4 * voxel)   # depth maps fused into a TSDF (libngp_meshtsdf.so); level 0
     m = extract_mesh(model, 512, tsdf=dict(K=K, poses=poses, img_wh=(W, H)), keep_largest=1)     # the surface the renders agree on
@@ -36,7 +39,8 @@
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
                               [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]]
-                              [--simplify-voxels K [--simplify-placement {mean,quadric}]] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
+                              [--simplify-voxels K [--simplify-placement {mean,quadric}]]
+                              [--decimate-faces N] [--decimate-max-error VOXELS] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
                               [--smooth-iterations N [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]]
                               [--texture-texels T [--score-cameras CAMS.npz [--score-out FILE.json]]]
                               [--distance-to REF.ply [--distance-spacing S] [--distance-thresholds T1,T2,...] [--distance-out FILE.json]]
@@ -60,8 +64,8 @@ import zlib
 import numpy as np
 import torch
 
-from . import (_lib, _mesh_lib, _meshcull_lib, _meshdist_lib, _meshfilter_lib, _meshquadric_lib, _meshsimplify_lib, _meshsmooth_lib,
-               _meshtex_lib, _meshtsdf_lib)
+from . import (_lib, _mesh_lib, _meshcull_lib, _meshdecimate_lib, _meshdist_lib, _meshfilter_lib, _meshquadric_lib, _meshsimplify_lib,
+               _meshsmooth_lib, _meshtex_lib, _meshtsdf_lib)
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -607,6 +611,89 @@ def simplify_clusters(mesh, cell, origin=None, placement="mean"):
     out[torch.where(used, rank, n_ov)] = positions
     m.vertices = out[:n_ov]
     return m
+
+
+def _decimate_args(target_faces, max_error, what="decimate"):
+    """target_faces as None or an int >= 0, max_error as None or a float that is finite and >= 0 (as a float32); at least one."""
+    if target_faces is None and max_error is None:
+        raise ValueError("%s needs target_faces, max_error or both" % what)
+    if target_faces is not None:
+        if isinstance(target_faces, bool) or not isinstance(target_faces, (int, np.integer)) or target_faces < 0:
+            raise ValueError("target_faces must be an int >= 0: %r" % (target_faces,))
+        target_faces = int(target_faces)
+    if max_error is not None:
+        try:
+            max_error = float(max_error)
+        except (TypeError, ValueError):
+            raise ValueError("max_error must be a number: %r" % (max_error,))
+        if not (math.isfinite(max_error) and max_error >= 0 and math.isfinite(C.c_float(max_error).value)):
+            raise ValueError("max_error must be finite and >= 0 (as a float32): %r" % (max_error,))
+    return target_faces, max_error
+
+
+def _decimate(v, f, extra, cell, target_faces, max_error):
+    """begin, then per round: round, one host read of its totals, apply; count, one host read, emit -> the decimated Mesh and the
+    stats (rounds, totals (R, 4): candidates, winners, faces, applied; reached; faces).  The loop is include/ngp_meshdecimate.h's."""
+    n_v, n_f, dev = v.shape[0], f.shape[0], v.device
+    normals, colors = extra
+    rows, left, n_ov, n_of = [], None, 0, 0
+    if n_v and n_f:
+        L = _meshdecimate_lib
+        ws_bytes = L.lib().ngp_meshdecimate_workspace_bytes(n_v, n_f)
+        if ws_bytes == 0:
+            raise ValueError("more than %d faces" % L.MAX_FACES)
+        e = -1.0 if max_error is None else max_error
+        with device_guard(dev):
+            s = stream()
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            totals = torch.empty(3, dtype=torch.int64, device=dev)
+            L.call("ngp_meshdecimate_begin", ptr(f), n_v, n_f, ptr(ws), ws_bytes, s)
+            while left is None or target_faces is None or left > target_faces:
+                L.call("ngp_meshdecimate_round", ptr(v), n_v, n_f, cell, e, ptr(ws), ws_bytes, ptr(totals), s)
+                n_c, n_w, left = totals.tolist()
+                if (target_faces is not None and left <= target_faces) or n_c == 0:
+                    rows.append([n_c, n_w, left, 0])
+                    break
+                n_keep = n_w if target_faces is None else min(n_w, (left - target_faces + 1) // 2)
+                L.call("ngp_meshdecimate_apply", n_v, n_f, n_w, n_keep, ptr(ws), ws_bytes, s)
+                rows.append([n_c, n_w, left, n_keep])
+                left -= 2 * n_keep                       # an applied collapse removes exactly the two faces on its edge
+            sizes = torch.empty(2, dtype=torch.int64, device=dev)
+            L.call("ngp_meshdecimate_count", n_v, n_f, ptr(ws), ws_bytes, ptr(sizes), s)
+            n_ov, n_of = sizes.tolist()
+    out = [torch.empty(n_ov, 3, dtype=torch.float32, device=dev) if a is not None else None for a in (v, normals, colors)]
+    faces = torch.empty(n_of, 3, dtype=torch.int32, device=dev)
+    if n_ov or n_of:
+        with device_guard(dev):
+            _meshdecimate_lib.call("ngp_meshdecimate_emit", ptr(v), ptr(normals), ptr(colors), n_v, n_f, ptr(ws), ws_bytes, n_ov, n_of,
+                                   ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(faces), stream())
+    stats = dict(rounds=sum(1 for r in rows if r[3] > 0), totals=torch.tensor(rows, dtype=torch.int64).reshape(-1, 4),
+                 reached=target_faces is None or n_of <= target_faces, faces=n_of)
+    return Mesh(out[0], faces, out[1], out[2]), stats
+
+
+def decimate(mesh, cell, target_faces=None, max_error=None, return_stats=False):
+    """The mesh after rounds of half-edge collapses (libngp_meshdecimate.so; include/ngp_meshdecimate.h has the exact rule), until
+    at most target_faces faces are left, or, without target_faces, until no collapse is left that keeps the collapsed vertex within
+    max_error (world units) of the planes of the faces it drags along; with both, the budget under the bound.  A collapse u -> v
+    merges u into a neighbour v: no vertex moves or appears, so the output vertices are input vertices, in their order, with their
+    positions, normals and colours bit for bit, and the faces keep their order and orientation.  Only a vertex inside a closed,
+    consistently oriented fan of 3..64 faces is ever removed: boundaries, non-manifold edges and bow-ties stay as they are, and a
+    closed oriented manifold stays one (link condition, no flipped face, no doubled face).  The cost of a collapse is the summed
+    area * squared plane distance of the faces it moves, an integer in units of cell^3 / 2^20: `cell` is that unit only, as in
+    smooth_taubin; every round applies an independent set of the cheapest collapses.  The result is the same on every run and for
+    any order of the faces.  A closed mesh that can reach the budget ends at target_faces or one below.
+    target_faces >= F returns the mesh itself.  Vertices no face references are dropped.  return_stats=True adds a dict: rounds,
+    totals ((R, 4) i64 per evaluated round: candidates, winners, faces before, collapses applied), reached, faces.
+    One host sync per round and one for the output sizes."""
+    target_faces, max_error = _decimate_args(target_faces, max_error)
+    cell, _ = _grid(cell, None)
+    v, f, extra = _check_mesh(mesh)
+    if target_faces is not None and target_faces >= f.shape[0]:
+        stats = dict(rounds=0, totals=torch.zeros(0, 4, dtype=torch.int64), reached=True, faces=f.shape[0])
+        return (mesh, stats) if return_stats else mesh
+    m, stats = _decimate(v, f, extra, cell, target_faces, max_error)
+    return (m, stats) if return_stats else m
 
 
 @dataclasses.dataclass
@@ -1242,6 +1329,18 @@ def _smooth_options(smooth):
     return dict(iterations=iterations, lam=lam, mu=mu, pin_boundary=bool(opts.get("pin_boundary", True)))
 
 
+def _decimate_options(decimate):
+    """extract_mesh's `decimate`: None, an int (target_faces) or dict(target_faces=, max_error=) with max_error in voxels -> None or
+    the checked (target_faces, max_error in voxels)."""
+    if decimate is None:
+        return None
+    opts = dict(decimate) if isinstance(decimate, dict) else dict(target_faces=decimate)
+    unknown = set(opts) - {"target_faces", "max_error"}
+    if unknown:
+        raise ValueError("decimate: unknown keys %r" % sorted(unknown))
+    return _decimate_args(opts.get("target_faces"), opts.get("max_error"))
+
+
 def _tsdf(model, resolution, lo, hi, K, poses, img_wh, trunc_voxels=4.0, min_opacity=0.5, depths=None):
     """The TSDF volume of extract_mesh(tsdf=dict(...)): the depth maps rendered from the model unless given, trunc in voxels of the
     largest lattice spacing."""
@@ -1255,12 +1354,14 @@ def _tsdf(model, resolution, lo, hi, K, poses, img_wh, trunc_voxels=4.0, min_opa
 
 
 def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None, simplify_voxels=None, tsdf=None,
-             smooth=None, texture=None, simplify_placement="mean"):
+             smooth=None, texture=None, simplify_placement="mean", decimate=None):
     """extract_mesh (with `texture`: baked after the simplification and the colours, before the smoothing), (components found, components kept) when a filter option is set (else None), the number of faces the cull
     dropped when `cull` is set (else None), (V0, V1, F0, F1) around the simplification when simplify_voxels is set (else None), and
-    (pairs, the topology's totals (4,) i64 on the device or None) when `smooth` is set (else None)."""
+    (pairs, the topology's totals (4,) i64 on the device or None) when `smooth` is set (else None).  With `decimate` the tuple of the
+    simplification covers the decimation too (the sizes before the first and after the last of the two)."""
     smooth = _smooth_options(smooth)
     texture = _texture_options(texture)
+    decimate = _decimate_options(decimate)
     if simplify_voxels is not None and not (math.isfinite(float(simplify_voxels)) and float(simplify_voxels) > 0):
         raise ValueError("simplify_voxels must be a finite number > 0: %r" % (simplify_voxels,))
     simplify_placement = _placement(simplify_placement, "simplify_placement")
@@ -1295,6 +1396,13 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
         before = (m.vertices.shape[0], m.faces.shape[0])
         m = simplify_clusters(m, cell, origin=lo, placement=simplify_placement)
         simplified = (before[0], m.vertices.shape[0], before[1], m.faces.shape[0])
+    if decimate is not None:
+        voxel, _ = _grid(max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution))), None)
+        before = (m.vertices.shape[0], m.faces.shape[0]) if simplified is None else (simplified[0], simplified[2])
+        v, f, extra = _check_mesh(m)
+        if decimate[0] is None or decimate[0] < f.shape[0]:
+            m = _decimate(v, f, extra, voxel, decimate[0], None if decimate[1] is None else decimate[1] * voxel)[0]
+        simplified = (before[0], m.vertices.shape[0], before[1], m.faces.shape[0])
     if colors:
         m.colors = vertex_colors(model, m.vertices, m.normals)
     baked = None
@@ -1312,7 +1420,7 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
 
 
 def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None, cull=None,
-                 simplify_voxels=None, tsdf=None, smooth=None, texture=None, simplify_placement="mean"):
+                 simplify_voxels=None, tsdf=None, smooth=None, texture=None, simplify_placement="mean", decimate=None):
     """density_volume + marching_cubes in the model's world coordinates; keep_largest / min_component_faces filter the components
     (filter_components); cull=dict(K=, poses=, img_wh=, min_views=1, bias=None) then drops the faces none of those cameras sees
     (cull_invisible; bias=None is twice the largest lattice spacing); simplify_voxels=K then merges the vertices of every grid
@@ -1330,9 +1438,12 @@ def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=Fals
     texture=T, or dict(texels=T), adds bake_texture with T texels per face leg: after the simplification, and BEFORE the smoothing if
     there is any -- the faces do not change under smoothing, so the baked texture belongs to the smoothed mesh, and the texels are
     sampled on the surface the field defines and along minus the gradient normals, the rule `colors` follows.  Without it
-    mesh.texture is None and everything else is the same bits."""
+    mesh.texture is None and everything else is the same bits.
+    decimate=N, or dict(target_faces=N, max_error=VOXELS), adds `decimate` after simplify_voxels and before the colours, the texture
+    and the smoothing, which see the decimated mesh as they see the clustered one: cell is the largest lattice spacing and
+    max_error is given in units of it.  Without it nothing new runs or loads."""
     return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels, tsdf, smooth,
-                    texture, simplify_placement)[0]
+                    texture, simplify_placement, decimate)[0]
 
 
 def _np(a):
@@ -1484,6 +1595,11 @@ def main(argv=None):
     ap.add_argument("--simplify-placement", default=None, choices=PLACEMENTS,
                     help="where a merged vertex goes: the mean of its cell's vertices (the default), or the point nearest the planes of "
                          "the faces around them (quadric), which keeps creases sharp; needs --simplify-voxels")
+    ap.add_argument("--decimate-faces", type=int, default=None, metavar="N",
+                    help="collapse edges until at most N faces are left (greedy, cheapest plane-distance error first), after --simplify-voxels")
+    ap.add_argument("--decimate-max-error", type=float, default=None, metavar="VOXELS",
+                    help="collapse an edge only while the moved faces' planes stay within this many voxels of the removed vertex; "
+                         "alone: collapse everything that does")
     ap.add_argument("--tsdf-cameras", default=None, metavar="FILE.npz",
                     help="mesh the TSDF fusion of the depth maps these cameras render instead of the thresholded density: an .npz as "
                          "--cull-cameras takes (--threshold is then not used)")
@@ -1516,6 +1632,10 @@ def main(argv=None):
         ap.error("--simplify-voxels takes K > 0")
     if a.simplify_placement is not None and a.simplify_voxels is None:
         ap.error("--simplify-placement needs --simplify-voxels")
+    if a.decimate_faces is not None and a.decimate_faces < 0:
+        ap.error("--decimate-faces takes N >= 0")
+    if a.decimate_max_error is not None and not (math.isfinite(a.decimate_max_error) and a.decimate_max_error >= 0):
+        ap.error("--decimate-max-error takes VOXELS >= 0")
     if not (math.isfinite(a.tsdf_trunc_voxels) and a.tsdf_trunc_voxels > 0):
         ap.error("--tsdf-trunc-voxels takes T > 0")
     if a.smooth_iterations is not None and a.smooth_iterations < 0:
@@ -1562,8 +1682,12 @@ def main(argv=None):
     smooth = None
     if a.smooth_iterations is not None:
         smooth = dict(iterations=a.smooth_iterations, lam=a.smooth_lambda, mu=a.smooth_mu, pin_boundary=not a.smooth_free_boundary)
+    decimate_opts = None
+    if a.decimate_faces is not None or a.decimate_max_error is not None:
+        decimate_opts = dict(target_faces=a.decimate_faces, max_error=a.decimate_max_error)
     m, found, culled, simplified, smoothed = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull,
-                                                      a.simplify_voxels, tsdf, smooth, a.texture_texels, a.simplify_placement or "mean")
+                                                      a.simplify_voxels, tsdf, smooth, a.texture_texels, a.simplify_placement or "mean",
+                                                      decimate_opts)
     if obj:
         save_obj(a.out, m)
     else:
