@@ -27,6 +27,9 @@
   libngp_meshdecimate.so -- decimation of a mesh to a face budget or an error bound by rounds of independent half-edge collapses
                      (integer plane-distance costs, claim words, the shared compaction) behind include/ngp_meshdecimate.h; its
                      sources live under csrc/meshdecimate/.
+  libngp_meshatlas.so -- the texture atlas with texel density by face size (a class per face from its longest edge, a stable
+                     16-bucket counting sort, one band of cells per class, texel points, UVs) and its renderer behind
+                     csrc/meshatlas/ngp_meshatlas.h, which lies beside its sources under csrc/meshatlas/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -100,6 +103,11 @@ MESHDECIMATE_SOURCES = [os.path.join("meshdecimate", "meshdecimate.hip")]
 MESHDECIMATE_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshdecimate.h")]
 # cross products, the flip and error tests and the rounding of the costs to int64 are the plain f64 expressions of include/ngp_meshdecimate.h, as tests/mesh_decimate_reference.py has them
 MESHDECIMATE_CFLAGS = ["-ffp-contract=off"]
+MESHATLAS_LIB = os.path.join(CSRC, "libngp_meshatlas.so")
+MESHATLAS_SOURCES = [os.path.join("meshatlas", "meshatlas.hip")]
+MESHATLAS_HEADERS = [os.path.join("meshatlas", "ngp_meshatlas.h")]
+# edge lengths, class thresholds, texel points, projection, barycentric weights and the bilinear lookup are the plain f32 expressions of csrc/meshatlas/ngp_meshatlas.h, as tests/mesh_atlas_reference.py has them
+MESHATLAS_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -141,8 +149,9 @@ def build(force=False, verbose=False):
     dist_objs, dist_jobs = _plan(MESHDIST_SOURCES, MESHDIST_HEADERS, lambda src: MESHDIST_CFLAGS, force)
     quadric_objs, quadric_jobs = _plan(MESHQUADRIC_SOURCES, MESHQUADRIC_HEADERS, lambda src: MESHQUADRIC_CFLAGS, force)
     decimate_objs, decimate_jobs = _plan(MESHDECIMATE_SOURCES, MESHDECIMATE_HEADERS, lambda src: MESHDECIMATE_CFLAGS, force)
+    atlas_objs, atlas_jobs = _plan(MESHATLAS_SOURCES, MESHATLAS_HEADERS, lambda src: MESHATLAS_CFLAGS, force)
     todo = (jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs + dist_jobs
-            + quadric_jobs + decimate_jobs)
+            + quadric_jobs + decimate_jobs + atlas_jobs)
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -153,7 +162,7 @@ def build(force=False, verbose=False):
                             (MESHTSDF_LIB, tsdf_objs, tsdf_jobs), (MESHSMOOTH_LIB, smooth_objs, smooth_jobs),
                             (MESHTEX_LIB, tex_objs, tex_jobs), (METRICS_LIB, metrics_objs, metrics_jobs),
                             (MESHDIST_LIB, dist_objs, dist_jobs), (MESHQUADRIC_LIB, quadric_objs, quadric_jobs),
-                            (MESHDECIMATE_LIB, decimate_objs, decimate_jobs)):
+                            (MESHDECIMATE_LIB, decimate_objs, decimate_jobs), (MESHATLAS_LIB, atlas_objs, atlas_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

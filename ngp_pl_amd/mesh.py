@@ -29,6 +29,9 @@
     m = bake_texture(model, m, texels=8)                           # the field's colour at every texel -> m.texture.image (H, W, 3) u8
     img = render_textured(m, K, poses, (W, H))                     # (C, H, W, 3) f32: the textured mesh seen from the cameras
     m = extract_mesh(model, 512, keep_largest=1, simplify_voxels=2, smooth=10, texture=8)        # baked after the simplification, before the smoothing
+    t = texture_atlas(m, texel_size=voxel)                         # AdaptiveTexture: texels per face by its longest edge, one band per class (libngp_meshatlas.so)
+    s = fit_texel_size(m, max_side=4096)                           # the smallest probed texel_size whose atlas fits 4096 x 4096
+    m = extract_mesh(model, 512, decimate=200000, texture=dict(texel_size=1.0))                  # the atlas for faces of unequal size
     r = compare_renders(model, m, K, poses, (W, H))                # PSNR and SSIM of the textured mesh's renders against the field's (libngp_metrics.so)
     p, w, i = sample_surface(m, spacing=voxel)                     # deterministic area samples: points, areas, face ids (libngp_meshdist.so)
     d, i = closest_on_mesh(p, m2)                                  # distance to and index of the nearest face of m2, exactly the brute-force minimum
@@ -42,7 +45,8 @@
                               [--simplify-voxels K [--simplify-placement {mean,quadric}]]
                               [--decimate-faces N] [--decimate-max-error VOXELS] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
                               [--smooth-iterations N [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]]
-                              [--texture-texels T [--score-cameras CAMS.npz [--score-out FILE.json]]]
+                              [--texture-texels T | --texture-texel-size VOXELS | --texture-max-side N [--texture-min-texels T] [--texture-max-texels T]
+                               [--score-cameras CAMS.npz [--score-out FILE.json]]]
                               [--distance-to REF.ply [--distance-spacing S] [--distance-thresholds T1,T2,...] [--distance-out FILE.json]]
                               --out mesh.ply | mesh.obj
 
@@ -66,6 +70,7 @@ import torch
 
 from . import (_lib, _mesh_lib, _meshcull_lib, _meshdecimate_lib, _meshdist_lib, _meshfilter_lib, _meshquadric_lib, _meshsimplify_lib,
                _meshsmooth_lib, _meshtex_lib, _meshtsdf_lib)
+from . import _meshatlas_lib                                      # binds libngp_meshatlas.so only when an AdaptiveTexture is asked for
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -819,6 +824,21 @@ class Texture:
     image: object = None        # (H, W, 3) u8, row 0 on top; None before baking
 
 
+@dataclasses.dataclass
+class AdaptiveTexture:
+    texel_size: float           # world units per texel interval: no edge is sampled coarser unless max_texels caps it
+    min_texels: int             # the ladder values that bound a face's T
+    max_texels: int
+    width: int                  # atlas width in texels
+    height: int
+    counts: tuple               # faces per class of the ladder _meshatlas_lib.LADDER (16 ints)
+    order: object               # (F,) i32: the faces by class descending, index ascending
+    face_place: object          # (F, 2) i32: cell origin, class and slot of every face (csrc/meshatlas/ngp_meshatlas.h)
+    face_texels: object         # (F,) i32: T of every face
+    uvs: object                 # (F, 3, 2) f32: u, v of every face's corners, OBJ's bottom-left origin
+    image: object = None        # (H, W, 3) u8, row 0 on top; None before baking
+
+
 def _texels(texels):
     if isinstance(texels, bool) or not isinstance(texels, (int, np.integer)) or not 1 <= texels <= 256:
         raise ValueError("texels must be an int in 1..256: %r" % (texels,))
@@ -838,10 +858,116 @@ def _atlas(n_faces, texels):
     return c.value, w.value, h.value
 
 
-def texture_atlas(mesh, texels=8):
+def _ladder_class(value, name):
+    """The class of a ladder value (ValueError for anything else)."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) not in _meshatlas_lib.LADDER:
+        raise ValueError("%s must be one of %r: %r" % (name, _meshatlas_lib.LADDER, value))
+    return _meshatlas_lib.LADDER.index(int(value))
+
+
+def _adaptive_args(texel_size, min_texels, max_texels):
+    """-> (texel_size as a float that is an f32, cmin, cmax), checked."""
+    if isinstance(texel_size, bool) or not isinstance(texel_size, (int, float, np.integer, np.floating)):
+        raise ValueError("texel_size must be a finite number > 0: %r" % (texel_size,))
+    with np.errstate(all="ignore"):
+        s = float(np.float32(texel_size))
+    if not (math.isfinite(s) and s > 0):
+        raise ValueError("texel_size must be a finite number > 0 (as a float32): %r" % (texel_size,))
+    cmin, cmax = _ladder_class(min_texels, "min_texels"), _ladder_class(max_texels, "max_texels")
+    if cmin > cmax:
+        raise ValueError("min_texels %d is above max_texels %d" % (min_texels, max_texels))
+    return s, cmin, cmax
+
+
+def _classify(v, f, s, cmin, cmax):
+    """ngp_meshatlas_classify -> face_class (F,) u8, order (F,) i32, counts (16,) i64, all on the device.  No host sync."""
+    dev, n_f = v.device, f.shape[0]
+    face_class = torch.empty(n_f, dtype=torch.uint8, device=dev)
+    order = torch.empty(n_f, dtype=torch.int32, device=dev)
+    counts = torch.empty(_meshatlas_lib.CLASSES, dtype=torch.int64, device=dev)
+    with device_guard(dev):
+        nbytes = _meshatlas_lib.lib().ngp_meshatlas_classify_workspace_bytes(n_f)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        _meshatlas_lib.call("ngp_meshatlas_classify", ptr(v), ptr(f), v.shape[0], n_f, s, cmin, cmax, ptr(face_class), ptr(order),
+                            ptr(counts), ptr(ws), ws.numel() * 8, stream())
+    return face_class, order, counts
+
+
+def _counts_array(counts):
+    return (C.c_int64 * _meshatlas_lib.CLASSES)(*[int(c) for c in counts])
+
+
+def _adaptive_atlas(mesh, texel_size, min_texels, max_texels):
+    s, cmin, cmax = _adaptive_args(texel_size, min_texels, max_texels)
+    if isinstance(mesh.faces, torch.Tensor) and mesh.faces.dim() == 2 and mesh.faces.shape[0] == 0:
+        raise ValueError("the mesh has no faces: there is nothing to put into an atlas")
+    v, f, _ = _check_mesh(mesh)
+    dev, n_f = v.device, f.shape[0]
+    face_class, order, counts_dev = _classify(v, f, s, cmin, cmax)
+    counts = tuple(counts_dev.cpu().tolist())                       # the one host read: 128 bytes
+    w, h, _ = _meshatlas_lib.layout(counts)
+    face_place = torch.empty(n_f, 2, dtype=torch.int32, device=dev)
+    uvs = torch.empty(n_f, 3, 2, dtype=torch.float32, device=dev)
+    with device_guard(dev):
+        _meshatlas_lib.call("ngp_meshatlas_place", ptr(order), _counts_array(counts), n_f, ptr(face_place), stream())
+        _meshatlas_lib.call("ngp_meshatlas_face_uvs", ptr(face_place), n_f, w, h, ptr(uvs), stream())
+    ladder = torch.tensor(_meshatlas_lib.LADDER, dtype=torch.int32, device=dev)
+    return AdaptiveTexture(s, int(min_texels), int(max_texels), w, h, counts, order, face_place, ladder[face_class.long()], uvs)
+
+
+def fit_texel_size(mesh, max_side, min_texels=1, max_texels=256, probes=24):
+    """The smallest PROBED texel_size whose atlas (texture_atlas(mesh, texel_size=...)) is at most max_side texels wide and high: a
+    bisection on log2(texel_size) between a size at which every face has min_texels and one at which every face has max_texels,
+    `probes` steps of one classification and one host read of the 16 class counts each.  It is the smallest probed value, not the
+    smallest there is: the atlas height is not strictly monotone in texel_size, since a band can gain a row when a face changes
+    class.  ValueError if even the coarsest atlas does not fit."""
+    if isinstance(max_side, bool) or not isinstance(max_side, (int, np.integer)) or not 1 <= max_side <= 16384:
+        raise ValueError("max_side must be an int in 1..16384: %r" % (max_side,))
+    if isinstance(probes, bool) or not isinstance(probes, (int, np.integer)) or probes < 1:
+        raise ValueError("probes must be an int >= 1: %r" % (probes,))
+    _, cmin, cmax = _adaptive_args(1.0, min_texels, max_texels)
+    if isinstance(mesh.faces, torch.Tensor) and mesh.faces.dim() == 2 and mesh.faces.shape[0] == 0:
+        raise ValueError("the mesh has no faces: there is nothing to put into an atlas")
+    v, f, _ = _check_mesh(mesh)
+
+    def fits(s):
+        try:
+            w, h, _ = _meshatlas_lib.layout(_classify(v, f, s, cmin, cmax)[2].cpu().tolist())
+        except ValueError:
+            return False
+        return max(w, h) <= max_side
+
+    # no edge is longer than 2 sqrt(3) times the largest finite coordinate
+    longest = 4.0 * float(torch.nan_to_num(v, nan=0.0, posinf=0.0, neginf=0.0).abs().max().cpu()) if v.shape[0] else 1.0
+    longest = longest if math.isfinite(longest) and longest > 0 else 1.0
+    hi = math.log2(longest) + 1.0                       # every finite face has min_texels here
+    lo = hi - 40.0
+    s_hi = float(np.float32(2.0 ** hi))
+    if not fits(s_hi):
+        raise ValueError("even with min_texels = %d for every face the atlas is larger than %d texels: simplify the mesh" % (min_texels, max_side))
+    best = s_hi
+    for _ in range(int(probes)):
+        mid = 0.5 * (lo + hi)
+        s = float(np.float32(2.0 ** mid))
+        if fits(s):
+            best, hi = s, mid
+        else:
+            lo = mid
+    return best
+
+
+def texture_atlas(mesh, texels=8, texel_size=None, min_texels=1, max_texels=256):
     """The atlas layout and the UVs of the mesh's faces (include/ngp_meshtex.h has the exact rule): every face is a right triangle
     with legs of `texels` texel intervals, two faces to a cell of (texels + 5) x (texels + 4) texels with a one-texel extrapolated
-    border round each, the cells in rows that make the atlas about square.  Returns a Texture without an image.  No host sync."""
+    border round each, the cells in rows that make the atlas about square.  Returns a Texture without an image.  No host sync.
+    With texel_size (world units per texel interval) every face instead gets the smallest T of the ladder 1, 2, 3, 4, 6, 8, ..., 256
+    inside [min_texels, max_texels] at which its longest edge is sampled no coarser than texel_size, the faces are sorted by T and
+    every T has a band of cells of its own (csrc/meshatlas/ngp_meshatlas.h has the exact rule; libngp_meshatlas.so): an AdaptiveTexture
+    without an image, after one host read of the 16 class counts.  texels and texel_size exclude each other."""
+    if texel_size is not None:
+        if not (isinstance(texels, (int, np.integer)) and not isinstance(texels, bool) and texels == 8):
+            raise ValueError("texels and texel_size exclude each other: give one of them")
+        return _adaptive_atlas(mesh, texel_size, min_texels, max_texels)
     texels = _texels(texels)
     if isinstance(mesh.faces, torch.Tensor) and mesh.faces.dim() == 2 and mesh.faces.shape[0] == 0:
         raise ValueError("the mesh has no faces: there is nothing to put into an atlas")
@@ -869,10 +995,36 @@ def _texel_points(v, f, normals, texture, b6, begin, count, out=None):
     if out is None:
         out = (torch.empty(count, 3, dtype=torch.float32, device=dev), torch.empty(count, 3, dtype=torch.float32, device=dev),
                torch.empty(count, dtype=torch.uint8, device=dev))
+    if isinstance(texture, AdaptiveTexture):
+        with device_guard(dev):
+            _meshatlas_lib.call("ngp_meshatlas_texel_points", ptr(v), ptr(f), ptr(normals), v.shape[0], f.shape[0], ptr(texture.order),
+                                _counts_array(texture.counts), b6, begin, count, ptr(out[0]), ptr(out[1]), ptr(out[2]), stream())
+        return out
     with device_guard(dev):
         _meshtex_lib.call("ngp_meshtex_texel_points", ptr(v), ptr(f), ptr(normals), v.shape[0], f.shape[0], texture.texels, b6, begin, count,
                           ptr(out[0]), ptr(out[1]), ptr(out[2]), stream())
     return out
+
+
+def _check_adaptive(texture, n_faces, device):
+    """An AdaptiveTexture that belongs to a mesh of n_faces faces on `device` (ValueError otherwise)."""
+    counts = texture.counts
+    try:
+        ok = len(counts) == _meshatlas_lib.CLASSES and all(int(c) >= 0 for c in counts) and sum(int(c) for c in counts) == n_faces
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("the texture's class counts %r are not those of a mesh of %d faces" % (counts, n_faces))
+    w, h, _ = _meshatlas_lib.layout(counts)
+    if (texture.width, texture.height) != (w, h):
+        raise ValueError("the texture's size %r x %r is not the layout of its class counts (%d x %d)" % (texture.width, texture.height, w, h))
+    for name, shape in (("order", (n_faces,)), ("face_place", (n_faces, 2))):
+        t = getattr(texture, name)
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("texture.%s must be a contiguous int32 tensor of shape %r" % (name, shape))
+        _require_cuda(t, "texture." + name)
+        if t.device != device:
+            raise ValueError("texture.%s is on %s, the mesh on %s" % (name, t.device, device))
 
 
 def _check_texture(texture, n_faces):
@@ -890,7 +1042,10 @@ def texel_points(mesh, texture, box, begin=0, count=None):
     ((0, 0, 1) where that is zero or not finite), and whether the texel belongs to a face with indices in range and a finite
     point.  mesh.normals must be set.  No host sync."""
     v, f, extra = _check_mesh(mesh)
-    _check_texture(texture, f.shape[0])
+    if isinstance(texture, AdaptiveTexture):
+        _check_adaptive(texture, f.shape[0], v.device)
+    else:
+        _check_texture(texture, f.shape[0])
     if extra[0] is None:
         raise ValueError("mesh.normals must be set: the texel directions come from them (vertex_normals(mesh) gives geometric ones)")
     b6 = _box6(box)
@@ -907,16 +1062,17 @@ def _quantise(c):
 
 
 @torch.no_grad()
-def bake_texture(model, mesh, texels=8, chunk=1 << 20, color_fn=None, box=None):
+def bake_texture(model, mesh, texels=8, chunk=1 << 20, color_fn=None, box=None, texel_size=None, min_texels=1, max_texels=256):
     """The mesh with .texture set: texture_atlas(mesh, texels) with the colour of every texel, evaluated `chunk` texels at a time
     at texel_points (inside the model's box; or `box` = (lo3, hi3), needed when model is None) by the model's no-grad forward, as
     vertex_colors uses it, or by color_fn(points (n, 3), dirs (n, 3)) -> (n, 3).  The image stores round(clamp(c, 0, 1) * 255),
-    halves to even, and 0 for invalid texels.  If mesh.normals is None the directions come from vertex_normals(mesh)."""
+    halves to even, and 0 for invalid texels.  If mesh.normals is None the directions come from vertex_normals(mesh).
+    texel_size, min_texels and max_texels are texture_atlas's: with texel_size the texture is an AdaptiveTexture."""
     if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
         raise ValueError("chunk must be an int >= 1: %r" % (chunk,))
     if model is None and (color_fn is None or box is None):
         raise ValueError("without a model both color_fn and box are needed")
-    t = texture_atlas(mesh, texels)
+    t = texture_atlas(mesh, texels, texel_size, min_texels, max_texels)
     v, f, extra = _check_mesh(mesh)
     normals = extra[0] if extra[0] is not None else _normals(v, f)
     b6 = _box6(box if box is not None else _box(model))
@@ -946,7 +1102,11 @@ def render_textured(mesh, K, poses, img_wh, background=(1, 1, 1), near=NEAR_DIST
     face index (C, H, W) i32 (-1 for none) and the depth (C, H, W) f32 (+inf for none).  No host sync."""
     _cameras(K, poses, img_wh)
     v, f, _ = _check_mesh(mesh)
-    texels = _check_texture(mesh.texture, f.shape[0])
+    adaptive = isinstance(mesh.texture, AdaptiveTexture)
+    if adaptive:
+        _check_adaptive(mesh.texture, f.shape[0], v.device)
+    else:
+        texels = _check_texture(mesh.texture, f.shape[0])
     img = mesh.texture.image
     if (not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or tuple(img.shape) != (mesh.texture.height, mesh.texture.width, 3)):
         raise ValueError("mesh.texture.image must be a (H, W, 3) uint8 tensor: bake_texture sets it")
@@ -968,6 +1128,12 @@ def render_textured(mesh, K, poses, img_wh, background=(1, 1, 1), near=NEAR_DIST
     depth = torch.empty(n_cams, H, W, dtype=torch.float32, device=dev) if return_ids else None
     with device_guard(dev):
         ws = torch.empty(fit, H, W, dtype=torch.int64, device=dev)
+        if adaptive:
+            t = mesh.texture
+            _meshatlas_lib.call("ngp_meshatlas_render", ptr(v), ptr(f), v.shape[0], f.shape[0], ptr(t.face_place), ptr(img), t.width,
+                                t.height, ptr(Kd), ptr(Pd), n_cams, W, H, near, (C.c_float * 3)(*bg), ptr(ws), ws.numel() * 8, ptr(image),
+                                ptr(ids), ptr(depth), stream())
+            return (image, ids, depth) if return_ids else image
         _meshtex_lib.call("ngp_meshtex_render", ptr(v), ptr(f), v.shape[0], f.shape[0], texels, ptr(img), ptr(Kd), ptr(Pd), n_cams,
                           W, H, near, (C.c_float * 3)(*bg), ptr(ws), ws.numel() * 8, ptr(image), ptr(ids), ptr(depth), stream())
     return (image, ids, depth) if return_ids else image
@@ -1307,13 +1473,28 @@ def mesh_distance(a, b, spacing=None, thresholds=(), max_dist=None, per_vertex=F
 
 
 def _texture_options(texture):
-    """extract_mesh's `texture`: None, an int (texels) or dict(texels=) -> None or the checked texels."""
+    """extract_mesh's `texture`: None, an int (texels), dict(texels=), dict(texel_size=VOXELS, min_texels=, max_texels=) or
+    dict(max_side=N, min_texels=, max_texels=) -> None, the checked texels, or the checked dict of the adaptive atlas."""
     if texture is None:
         return None
     opts = dict(texture) if isinstance(texture, dict) else dict(texels=texture)
-    unknown = set(opts) - {"texels"}
+    unknown = set(opts) - {"texels", "texel_size", "max_side", "min_texels", "max_texels"}
     if unknown:
         raise ValueError("texture: unknown keys %r" % sorted(unknown))
+    if "texel_size" in opts or "max_side" in opts:
+        if "texels" in opts or ("texel_size" in opts and "max_side" in opts):
+            raise ValueError("texture: texels, texel_size and max_side exclude each other: %r" % sorted(opts))
+        out = dict(min_texels=opts.get("min_texels", 1), max_texels=opts.get("max_texels", 256))
+        _adaptive_args(opts.get("texel_size", 1.0), out["min_texels"], out["max_texels"])
+        if "max_side" in opts:
+            if isinstance(opts["max_side"], bool) or not isinstance(opts["max_side"], (int, np.integer)) or not 1 <= opts["max_side"] <= 16384:
+                raise ValueError("texture: max_side must be an int in 1..16384: %r" % (opts["max_side"],))
+            out["max_side"] = int(opts["max_side"])
+        else:
+            out["texel_size"] = float(opts["texel_size"])
+        return out
+    if "min_texels" in opts or "max_texels" in opts:
+        raise ValueError("texture: min_texels and max_texels need texel_size or max_side")
     return _texels(opts.get("texels", 8))
 
 
@@ -1406,7 +1587,13 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
     if colors:
         m.colors = vertex_colors(model, m.vertices, m.normals)
     baked = None
-    if texture is not None:
+    if isinstance(texture, dict):                        # texel density by face size: texel_size in units of the largest lattice spacing
+        if "max_side" in texture:
+            size = fit_texel_size(m, texture["max_side"], texture["min_texels"], texture["max_texels"])
+        else:
+            size = texture["texel_size"] * max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution)))
+        baked = bake_texture(model, m, texel_size=size, min_texels=texture["min_texels"], max_texels=texture["max_texels"]).texture
+    elif texture is not None:
         baked = bake_texture(model, m, texture).texture
     smoothed = None
     if smooth is not None:
@@ -1439,6 +1626,10 @@ def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=Fals
     there is any -- the faces do not change under smoothing, so the baked texture belongs to the smoothed mesh, and the texels are
     sampled on the surface the field defines and along minus the gradient normals, the rule `colors` follows.  Without it
     mesh.texture is None and everything else is the same bits.
+    texture=dict(texel_size=VOXELS, min_texels=1, max_texels=256) bakes an AdaptiveTexture instead (texture_atlas with texel_size):
+    texel_size is given in units of the largest lattice spacing, as decimate's max_error is; texture=dict(max_side=N, ...) takes the
+    texel_size that fit_texel_size finds for an atlas of at most N x N texels.  This is the atlas for a decimated mesh, whose faces
+    differ in size.
     decimate=N, or dict(target_faces=N, max_error=VOXELS), adds `decimate` after simplify_voxels and before the colours, the texture
     and the smoothing, which see the decimated mesh as they see the clustered one: cell is the largest lattice spacing and
     max_error is given in units of it.  Without it nothing new runs or loads."""
@@ -1612,6 +1803,14 @@ def main(argv=None):
     ap.add_argument("--smooth-free-boundary", action="store_true", help="let the vertices of boundary edges move too")
     ap.add_argument("--texture-texels", type=int, default=None, metavar="T",
                     help="bake a texture atlas with T texels along every face's leg (1..256); needs an --out that ends in .obj")
+    ap.add_argument("--texture-texel-size", type=float, default=None, metavar="VOXELS",
+                    help="bake a texture atlas with texel density by face size instead: every face gets the fewest texels of the ladder "
+                         "1, 2, 3, 4, 6, 8, ..., 256 that sample its longest edge no coarser than VOXELS voxels per texel; the atlas for a "
+                         "decimated mesh; excludes --texture-texels")
+    ap.add_argument("--texture-max-side", type=int, default=None, metavar="N",
+                    help="as --texture-texel-size, with the smallest texel size found whose atlas is at most N x N texels")
+    ap.add_argument("--texture-min-texels", type=int, default=None, metavar="T", help="fewest texels along a face's leg (a ladder value; default 1)")
+    ap.add_argument("--texture-max-texels", type=int, default=None, metavar="T", help="most texels along a face's leg (a ladder value; default 256)")
     ap.add_argument("--score-cameras", default=None, metavar="FILE.npz",
                     help="score the textured mesh against the field's own renders from these cameras (PSNR, SSIM; compare_renders) and "
                          "print the record as one JSON line: an .npz as --cull-cameras takes; needs --texture-texels")
@@ -1644,13 +1843,34 @@ def main(argv=None):
         if not (math.isfinite(x) and abs(x) <= 1):
             ap.error("%s takes a finite factor of magnitude <= 1" % flag)
     obj = a.out.lower().endswith(".obj")
+    adaptive = a.texture_texel_size is not None or a.texture_max_side is not None
+    if adaptive and a.texture_texels is not None:
+        ap.error("--texture-texel-size and --texture-max-side exclude --texture-texels")
+    if a.texture_texel_size is not None and a.texture_max_side is not None:
+        ap.error("--texture-texel-size and --texture-max-side exclude each other")
+    if (a.texture_min_texels is not None or a.texture_max_texels is not None) and not adaptive:
+        ap.error("--texture-min-texels and --texture-max-texels need --texture-texel-size or --texture-max-side")
+    if a.texture_texel_size is not None and not (math.isfinite(a.texture_texel_size) and a.texture_texel_size > 0):
+        ap.error("--texture-texel-size takes VOXELS > 0")
+    if a.texture_max_side is not None and not 1 <= a.texture_max_side <= 16384:
+        ap.error("--texture-max-side takes N in 1..16384")
+    lo_t, hi_t = (1 if a.texture_min_texels is None else a.texture_min_texels), (256 if a.texture_max_texels is None else a.texture_max_texels)
+    if adaptive and (lo_t not in _meshatlas_lib.LADDER or hi_t not in _meshatlas_lib.LADDER or lo_t > hi_t):
+        ap.error("--texture-min-texels and --texture-max-texels take values of %s, min <= max" % (_meshatlas_lib.LADDER,))
+    if adaptive and not obj:
+        ap.error("--texture-texel-size and --texture-max-side need an --out that ends in .obj: a PLY carries no texture")
+    texture_opts = a.texture_texels
+    if a.texture_texel_size is not None:
+        texture_opts = dict(texel_size=a.texture_texel_size, min_texels=lo_t, max_texels=hi_t)
+    elif a.texture_max_side is not None:
+        texture_opts = dict(max_side=a.texture_max_side, min_texels=lo_t, max_texels=hi_t)
     if a.texture_texels is not None and not obj:
         ap.error("--texture-texels needs an --out that ends in .obj: a PLY carries no texture")
-    if obj and a.texture_texels is None:
-        ap.error("an .obj output needs --texture-texels T")
+    if obj and texture_opts is None:
+        ap.error("an .obj output needs --texture-texels T (or --texture-texel-size VOXELS, --texture-max-side N)")
     if a.texture_texels is not None and not 1 <= a.texture_texels <= 256:
         ap.error("--texture-texels takes T in 1..256")
-    if a.score_cameras is not None and a.texture_texels is None:
+    if a.score_cameras is not None and texture_opts is None:
         ap.error("--score-cameras needs --texture-texels: the score is of the textured mesh")
     if a.score_out is not None and a.score_cameras is None:
         ap.error("--score-out needs --score-cameras")
@@ -1686,7 +1906,7 @@ def main(argv=None):
     if a.decimate_faces is not None or a.decimate_max_error is not None:
         decimate_opts = dict(target_faces=a.decimate_faces, max_error=a.decimate_max_error)
     m, found, culled, simplified, smoothed = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull,
-                                                      a.simplify_voxels, tsdf, smooth, a.texture_texels, a.simplify_placement or "mean",
+                                                      a.simplify_voxels, tsdf, smooth, texture_opts, a.simplify_placement or "mean",
                                                       decimate_opts)
     if obj:
         save_obj(a.out, m)
@@ -1706,6 +1926,9 @@ def main(argv=None):
         line += ", smoothed %d pairs, %d of %d vertices free" % (smoothed[0], n_free, m.vertices.shape[0])
     if m.texture is not None:
         line += ", texture %d x %d" % (m.texture.width, m.texture.height)
+        if isinstance(m.texture, AdaptiveTexture):
+            line += ", texel size %.6g, faces per texels %s" % (
+                m.texture.texel_size, " ".join("%d:%d" % (t, n) for t, n in zip(_meshatlas_lib.LADDER, m.texture.counts) if n))
     print(line)
     if a.score_cameras is not None:
         import json
