@@ -64,6 +64,15 @@ def run_hash_fwd(lib, meta, x, table_h, mn=-0.5, mx=0.5):
     return feats
 
 
+def assert_within_derived_limit(feats, x, table, meta, half=0.5):
+    """Every output within its own limit of the exact value at the kernel's own cell (tests/hashgrid_forward_reference.py: hash forward,
+    exact cell, derived bound per output) -- next to, not instead of, the absolute tolerance against the oracle."""
+    from tests import hashgrid_forward_reference as F
+    ref = F.forward_reference(x.numpy(), [-half] * 3, [half] * 3, table.half().numpy(), meta.resolution, meta.offset, meta.scale, 16)
+    bad, what, _ = F.out_of_limit(feats.cpu().numpy(), ref)
+    assert bad == 0, "%d of %d outputs out of limit; %s" % (bad, feats.numel(), what)
+
+
 def test_grid_meta_matches_oracle(lib, field):
     meta = native_meta(lib)
     assert [meta.resolution[i] for i in range(16)] == field.meta.resolution
@@ -82,6 +91,7 @@ def test_hashgrid_forward(lib, field):
     want = T.hash_encode(x + 0.5, field.table, field.meta, quantize=True)
     # |values| <= 0.8, f16 storage: 1 ulp at that magnitude is 4.9e-4; allow 2 ulp
     np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=0, atol=1e-3)
+    assert_within_derived_limit(feats, x, field.table, meta)
     # row-major converters round-trip
     rm = torch.empty(x.shape[0], 32, dtype=torch.float16, device="cuda")
     lib.call("ngp_feats_to_rowmajor", lib.ptr(feats), 16, x.shape[0], lib.ptr(rm), lib.stream())
@@ -552,6 +562,7 @@ def test_exact_level_table_option(lib):
     got = feats.permute(1, 0, 2).reshape(x.shape[0], 32).float().cpu()
     want = T.hash_encode(x + 0.5, table, om, quantize=True)
     np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=0, atol=1e-3)
+    assert_within_derived_limit(feats, x, table, meta)
     n = x.shape[0]
     dfe = (torch.randn(n, 32, generator=g) * 0.5).half()
     tb = table.clone().requires_grad_(True)
