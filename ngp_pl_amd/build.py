@@ -30,6 +30,9 @@
   libngp_meshatlas.so -- the texture atlas with texel density by face size (a class per face from its longest edge, a stable
                      16-bucket counting sort, one band of cells per class, texel points, UVs) and its renderer behind
                      csrc/meshatlas/ngp_meshatlas.h, which lies beside its sources under csrc/meshatlas/.
+  libngp_meshphoto.so -- the colour of surface points blended from photographs (projection, a two-sided depth test against the
+                     mesh's depth buffers, a bilinear sample, a weight by viewing angle, serial per-point sums) behind
+                     csrc/meshphoto/ngp_meshphoto.h, which lies beside its sources under csrc/meshphoto/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -108,6 +111,11 @@ MESHATLAS_SOURCES = [os.path.join("meshatlas", "meshatlas.hip")]
 MESHATLAS_HEADERS = [os.path.join("meshatlas", "ngp_meshatlas.h")]
 # edge lengths, class thresholds, texel points, projection, barycentric weights and the bilinear lookup are the plain f32 expressions of csrc/meshatlas/ngp_meshatlas.h, as tests/mesh_atlas_reference.py has them
 MESHATLAS_CFLAGS = ["-ffp-contract=off"]
+MESHPHOTO_LIB = os.path.join(CSRC, "libngp_meshphoto.so")
+MESHPHOTO_SOURCES = [os.path.join("meshphoto", "meshphoto.hip")]
+MESHPHOTO_HEADERS = [os.path.join("meshphoto", "ngp_meshphoto.h")]
+# projection, the viewing angle, the depth test, the bilinear sample and the weighted sums are the plain f32 expressions of csrc/meshphoto/ngp_meshphoto.h, as tests/mesh_photo_reference.py has them
+MESHPHOTO_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -150,8 +158,9 @@ def build(force=False, verbose=False):
     quadric_objs, quadric_jobs = _plan(MESHQUADRIC_SOURCES, MESHQUADRIC_HEADERS, lambda src: MESHQUADRIC_CFLAGS, force)
     decimate_objs, decimate_jobs = _plan(MESHDECIMATE_SOURCES, MESHDECIMATE_HEADERS, lambda src: MESHDECIMATE_CFLAGS, force)
     atlas_objs, atlas_jobs = _plan(MESHATLAS_SOURCES, MESHATLAS_HEADERS, lambda src: MESHATLAS_CFLAGS, force)
+    photo_objs, photo_jobs = _plan(MESHPHOTO_SOURCES, MESHPHOTO_HEADERS, lambda src: MESHPHOTO_CFLAGS, force)
     todo = (jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs + dist_jobs
-            + quadric_jobs + decimate_jobs + atlas_jobs)
+            + quadric_jobs + decimate_jobs + atlas_jobs + photo_jobs)
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -162,7 +171,8 @@ def build(force=False, verbose=False):
                             (MESHTSDF_LIB, tsdf_objs, tsdf_jobs), (MESHSMOOTH_LIB, smooth_objs, smooth_jobs),
                             (MESHTEX_LIB, tex_objs, tex_jobs), (METRICS_LIB, metrics_objs, metrics_jobs),
                             (MESHDIST_LIB, dist_objs, dist_jobs), (MESHQUADRIC_LIB, quadric_objs, quadric_jobs),
-                            (MESHDECIMATE_LIB, decimate_objs, decimate_jobs), (MESHATLAS_LIB, atlas_objs, atlas_jobs)):
+                            (MESHDECIMATE_LIB, decimate_objs, decimate_jobs), (MESHATLAS_LIB, atlas_objs, atlas_jobs),
+                            (MESHPHOTO_LIB, photo_objs, photo_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

@@ -32,6 +32,9 @@
     t = texture_atlas(m, texel_size=voxel)                         # AdaptiveTexture: texels per face by its longest edge, one band per class (libngp_meshatlas.so)
     s = fit_texel_size(m, max_side=4096)                           # the smallest probed texel_size whose atlas fits 4096 x 4096
     m = extract_mesh(model, 512, decimate=200000, texture=dict(texel_size=1.0))                  # the atlas for faces of unequal size
+    c, ok, n = photo_colors(m, p, d, ok, images, K, poses, (W, H), bias=2 * voxel)               # colours blended from photographs (libngp_meshphoto.so)
+    m = bake_texture_from_images(m, images, K, poses, (W, H), texels=8, bias=2 * voxel, model=model)   # the atlas from the photographs, the field where none sees
+    m = extract_mesh(model, 512, decimate=200000, texture=dict(texel_size=1.0, images=dict(images=images, K=K, poses=poses, img_wh=(W, H))))
     r = compare_renders(model, m, K, poses, (W, H))                # PSNR and SSIM of the textured mesh's renders against the field's (libngp_metrics.so)
     p, w, i = sample_surface(m, spacing=voxel)                     # deterministic area samples: points, areas, face ids (libngp_meshdist.so)
     d, i = closest_on_mesh(p, m2)                                  # distance to and index of the nearest face of m2, exactly the brute-force minimum
@@ -46,6 +49,8 @@
                               [--decimate-faces N] [--decimate-max-error VOXELS] [--tsdf-cameras CAMS.npz [--tsdf-trunc-voxels T] [--tsdf-min-opacity O]]
                               [--smooth-iterations N [--smooth-lambda L] [--smooth-mu M] [--smooth-free-boundary]]
                               [--texture-texels T | --texture-texel-size VOXELS | --texture-max-side N [--texture-min-texels T] [--texture-max-texels T]
+                               [--texture-images PHOTOS.npz [--texture-image-bias B] [--texture-image-guard G] [--texture-image-min-cos C]
+                                [--texture-image-power P] [--texture-image-min-views N]]
                                [--score-cameras CAMS.npz [--score-out FILE.json]]]
                               [--distance-to REF.ply [--distance-spacing S] [--distance-thresholds T1,T2,...] [--distance-out FILE.json]]
                               --out mesh.ply | mesh.obj
@@ -71,6 +76,7 @@ import torch
 from . import (_lib, _mesh_lib, _meshcull_lib, _meshdecimate_lib, _meshdist_lib, _meshfilter_lib, _meshquadric_lib, _meshsimplify_lib,
                _meshsmooth_lib, _meshtex_lib, _meshtsdf_lib)
 from . import _meshatlas_lib                                      # binds libngp_meshatlas.so only when an AdaptiveTexture is asked for
+from . import _meshphoto_lib                                      # binds libngp_meshphoto.so only when a texture is baked from photographs
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -1093,6 +1099,159 @@ def bake_texture(model, mesh, texels=8, chunk=1 << 20, color_fn=None, box=None, 
     return dataclasses.replace(mesh, texture=t)
 
 
+def _photo_args(bias, guard, min_cos, power, min_views, near):
+    """-> (bias, guard, min_cos, power, min_views, near) checked against the ranges of csrc/meshphoto/ngp_meshphoto.h."""
+    def number(x, name):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError("%s must be a number: %r" % (name, x))
+        with np.errstate(all="ignore"):
+            return float(np.float32(x))
+
+    def integer(x, name, lo, hi):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not lo <= x <= hi:
+            raise ValueError("%s must be an int in %d..%d: %r" % (name, lo, hi, x))
+        return int(x)
+
+    b, c, nr = number(bias, "bias"), number(min_cos, "min_cos"), number(near, "near")
+    if not (math.isfinite(b) and b >= 0):
+        raise ValueError("bias must be finite and >= 0 (world units): %r" % (bias,))
+    if not 0 < c <= 1:
+        raise ValueError("min_cos must lie in (0, 1]: %r" % (min_cos,))
+    if not math.isfinite(nr):
+        raise ValueError("near must be finite: %r" % (near,))
+    return (b, integer(guard, "guard", 0, _meshphoto_lib.MAX_GUARD), c, integer(power, "power", 1, _meshphoto_lib.MAX_POWER),
+            integer(min_views, "min_views", 1, INT32_MAX), nr)
+
+
+def _photo_images(images, n_cams, W, H):
+    """images as a (C, H, W, 3) uint8 tensor, on the host or on the device (ValueError otherwise)."""
+    if isinstance(images, np.ndarray):
+        images = torch.from_numpy(np.ascontiguousarray(images))
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or tuple(images.shape) != (n_cams, H, W, 3):
+        raise ValueError("images must be a (%d, %d, %d, 3) uint8 array or tensor, one photograph (H, W, 3) per pose: %r"
+                         % (n_cams, H, W, (getattr(images, "dtype", None), tuple(getattr(images, "shape", ())))))
+    return images
+
+
+def _photo_colors(v, f, points, dirs, valid, images, Kd, Pd, W, H, args, max_workspace_bytes, cache=None):
+    """photo_colors on checked arguments.  cache: a dict that keeps the depth buffers and the uploaded photographs from one call to
+    the next when all the cameras fit one chunk (the texel chunks of bake_texture_from_images share them)."""
+    bias, guard, min_cos, power, min_views, near = args
+    dev, n, n_cams = v.device, points.shape[0], Pd.shape[0]
+    fit = max(1, min(n_cams, int(max_workspace_bytes) // (7 * W * H)))                  # 4 bytes of depth and 3 of colour per pixel
+    acc = torch.zeros(n, 4, dtype=torch.float32, device=dev)
+    views = torch.zeros(n, dtype=torch.int32, device=dev)
+    rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    seen = torch.empty(n, dtype=torch.uint8, device=dev)
+    for c0 in range(0, n_cams, fit):
+        nc = min(fit, n_cams - c0)
+        if cache is not None and "zbuf" in cache:
+            zbuf, img = cache["zbuf"], cache["images"]
+        else:
+            zbuf = _views(v, f, Kd, Pd[c0:c0 + nc], (W, H), bias, near, 4 * W * H * nc)[1]      # one chunk: (nc, H, W) depth bits
+            img = images[c0:c0 + nc].to(dev, non_blocking=True).contiguous()
+            if cache is not None and fit == n_cams:
+                cache["zbuf"], cache["images"] = zbuf, img
+        with device_guard(dev):
+            _meshphoto_lib.call("ngp_meshphoto_accumulate", ptr(points), ptr(dirs), ptr(valid), n, ptr(Kd), ptr(Pd[c0:c0 + nc]), nc, W, H,
+                                ptr(img), ptr(zbuf), near, bias, guard, min_cos, power, ptr(acc), ptr(views), stream())
+    with device_guard(dev):
+        _meshphoto_lib.call("ngp_meshphoto_resolve", ptr(acc), ptr(views), ptr(valid), n, min_views, ptr(rgb), ptr(seen), stream())
+    return rgb, seen, views
+
+
+def photo_colors(mesh, points, dirs, valid, images, K, poses, img_wh, bias, guard=1, min_cos=0.1, power=2, min_views=1, near=NEAR_DISTANCE,
+                 max_workspace_bytes=1 << 28):
+    """(rgb (n, 3) f32, seen (n,) u8, views (n,) i32): the colour of the surface points `points` (n, 3) f32 -- texels (texel_points),
+    vertices, anything on the mesh -- blended from the photographs images (C, H, W, 3) uint8 that the cameras K (3, 3), poses
+    (C, 3, 4) camera-to-world, img_wh = (W, H) took (csrc/meshphoto/ngp_meshphoto.h has the exact rule).  dirs (n, 3) f32 is the
+    direction a viewer looks along at each point, minus the normal; valid (n,) u8 switches points off.  A photograph counts for a
+    point when the point lies at or beyond `near`, its bilinear footprint lies inside the frame, the camera sees it at a cosine of
+    at least min_cos to the normal, and the mesh's depth in every pixel within `guard` pixels of its projection agrees with its own
+    depth to within `bias` (world units): an occluder, a silhouette or a hole nearby rejects it.  The colours are averaged with the
+    weight cosine ** power.  seen is 1 where at least min_views photographs counted, rgb is 0 elsewhere, views is their number.
+    The cameras go through the mesh's depth buffers (ngp_meshcull_views) and the device copy of their photographs, as many at a time
+    as fit max_workspace_bytes (7 bytes per pixel; at least one); the result does not depend on that.  images may live on the host:
+    every chunk is uploaded as it is used.  No host sync."""
+    args = _photo_args(bias, guard, min_cos, power, min_views, near)
+    _cameras(K, poses, img_wh)
+    v, f, _ = _check_mesh(mesh)
+    dev = v.device
+    Kd, Pd, W, H = _cameras(K, poses, img_wh, dev)
+    images = _photo_images(images, Pd.shape[0], W, H)
+    for name, t, shape, dtype in (("points", points, None, torch.float32), ("dirs", dirs, None, torch.float32), ("valid", valid, 1, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or (t.dim() != 1 if shape else (t.dim() != 2 or t.shape[1] != 3)):
+            raise ValueError("%s must be a %s tensor of %s" % (name, dtype, "shape (n,)" if shape else "shape (n, 3)"))
+        _require_cuda(t, name)
+        if t.device != dev:
+            raise ValueError("%s is on %s, the mesh on %s" % (name, t.device, dev))
+    if not (points.shape[0] == dirs.shape[0] == valid.shape[0]):
+        raise ValueError("points, dirs and valid differ in length: %d, %d, %d" % (points.shape[0], dirs.shape[0], valid.shape[0]))
+    return _photo_colors(v, f, points.contiguous(), dirs.contiguous(), valid.contiguous(), images, Kd, Pd, W, H, args, max_workspace_bytes)
+
+
+def _fill(fill):
+    try:
+        c = [float(x) for x in fill]
+    except (TypeError, ValueError):
+        c = []
+    if len(c) != 3 or not all(0.0 <= x <= 1.0 for x in c):
+        raise ValueError("fill must be three numbers in 0..1: %r" % (fill,))
+    return c
+
+
+@torch.no_grad()
+def bake_texture_from_images(mesh, images, K, poses, img_wh, texels=8, texel_size=None, min_texels=1, max_texels=256, bias=None, guard=1,
+                             min_cos=0.1, power=2, min_views=1, fill=None, model=None, box=None, chunk=1 << 20, return_seen=False):
+    """The mesh with .texture set, as bake_texture leaves it, the colour of every texel blended from the photographs that see it
+    (photo_colors at texel_points, `chunk` texels at a time; images, K, poses, img_wh, bias, guard, min_cos, power and min_views are
+    photo_colors's, and bias (world units, about two voxels of the lattice the mesh came from) must be given).  texels, or texel_size
+    with min_texels and max_texels, choose the atlas as in texture_atlas.  A valid texel that fewer than min_views photographs see
+    takes the field's colour when `model` is given, evaluated exactly as bake_texture does; otherwise `fill`, three numbers in 0..1
+    (default black).  Invalid texels are 0.  The texel points are clamped to the model's box, or to `box` = (lo3, hi3), which is
+    needed when model is None.  The image stores round(clamp(c, 0, 1) * 255), halves to even.  If mesh.normals is None the
+    directions come from vertex_normals(mesh).  return_seen=True also returns the (H, W) u8 map of the texels the photographs
+    coloured.  Baking twice gives the same bytes."""
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError("chunk must be an int >= 1: %r" % (chunk,))
+    if bias is None:
+        raise ValueError("bias must be given: the depth slack in world units (about two voxels of the lattice the mesh came from)")
+    args = _photo_args(bias, guard, min_cos, power, min_views, NEAR_DISTANCE)
+    if model is not None and fill is not None:
+        raise ValueError("model and fill exclude each other: unseen texels take the field's colour or the fill colour")
+    if model is None and box is None:
+        raise ValueError("without a model a box is needed")
+    fill = _fill((0, 0, 0) if fill is None else fill)
+    _cameras(K, poses, img_wh)
+    t = texture_atlas(mesh, texels, texel_size, min_texels, max_texels)
+    v, f, extra = _check_mesh(mesh)
+    dev = v.device
+    Kd, Pd, W, H = _cameras(K, poses, img_wh, dev)
+    images = _photo_images(images, Pd.shape[0], W, H)
+    normals = extra[0] if extra[0] is not None else _normals(v, f)
+    b6 = _box6(box if box is not None else _box(model))
+    n = t.width * t.height
+    image = torch.empty(n, 3, dtype=torch.uint8, device=dev)
+    seen_map = torch.empty(n, dtype=torch.uint8, device=dev)
+    fill_rgb = torch.tensor(fill, dtype=torch.float32, device=dev)
+    chunk = int(min(chunk, n))
+    buf, cache = None, {}
+    for begin in range(0, n, chunk):
+        cnt = min(chunk, n - begin)
+        if buf is not None and buf[0].shape[0] != cnt:   # the last, shorter chunk
+            buf = None
+        buf = p, d, ok = _texel_points(v, f, normals, t, b6, begin, cnt, buf)
+        rgb, seen, _ = _photo_colors(v, f, p, d, ok, images, Kd, Pd, W, H, args, 1 << 28, cache)
+        other = model(p, d)[1].float() if model is not None else fill_rgb.expand(cnt, 3)
+        if tuple(other.shape) != (cnt, 3):
+            raise ValueError("the model must return a (%d, 3) colour tensor" % cnt)
+        image[begin:begin + cnt] = _quantise(torch.where(seen.bool().unsqueeze(1), rgb, other)) * ok.unsqueeze(1)
+        seen_map[begin:begin + cnt] = seen
+    t.image = image.view(t.height, t.width, 3)
+    out = dataclasses.replace(mesh, texture=t)
+    return (out, seen_map.view(t.height, t.width)) if return_seen else out
+
+
 def render_textured(mesh, K, poses, img_wh, background=(1, 1, 1), near=NEAR_DISTANCE, max_workspace_bytes=1 << 28, return_ids=False):
     """(C, H, W, 3) f32: the mesh with its baked texture seen from the cameras K (3, 3), poses (C, 3, 4) camera-to-world, img_wh =
     (W, H) -- NGP.mark_invisible_cells' arguments.  Per pixel the nearest face that covers its centre (the cull's rasteriser rule;
@@ -1472,15 +1631,45 @@ def mesh_distance(a, b, spacing=None, thresholds=(), max_dist=None, per_vertex=F
     return res
 
 
+def _photo_options(images):
+    """The `images` entry of extract_mesh's `texture`: dict(images=, K=, poses=, img_wh=, bias=None, guard=1, min_cos=0.1, power=2,
+    min_views=1) -> the checked dict, every key present (bias=None: twice the largest lattice spacing, set by the caller)."""
+    if not isinstance(images, dict):
+        raise ValueError("texture: images must be a dict(images=, K=, poses=, img_wh=, ...): %r" % (type(images).__name__,))
+    opts = dict(images)
+    unknown = set(opts) - {"images", "K", "poses", "img_wh", "bias", "guard", "min_cos", "power", "min_views"}
+    if unknown:
+        raise ValueError("texture: images: unknown keys %r" % sorted(unknown))
+    missing = {"images", "K", "poses", "img_wh"} - set(opts)
+    if missing:
+        raise ValueError("texture: images: %r missing" % sorted(missing))
+    _cameras(opts["K"], opts["poses"], opts["img_wh"])
+    _photo_images(opts["images"], len(opts["poses"]), int(opts["img_wh"][0]), int(opts["img_wh"][1]))
+    out = dict(images=opts["images"], K=opts["K"], poses=opts["poses"], img_wh=(int(opts["img_wh"][0]), int(opts["img_wh"][1])),
+               bias=opts.get("bias"), guard=opts.get("guard", 1), min_cos=opts.get("min_cos", 0.1), power=opts.get("power", 2),
+               min_views=opts.get("min_views", 1))
+    _photo_args(0.0 if out["bias"] is None else out["bias"], out["guard"], out["min_cos"], out["power"], out["min_views"], NEAR_DISTANCE)
+    return out
+
+
 def _texture_options(texture):
     """extract_mesh's `texture`: None, an int (texels), dict(texels=), dict(texel_size=VOXELS, min_texels=, max_texels=) or
-    dict(max_side=N, min_texels=, max_texels=) -> None, the checked texels, or the checked dict of the adaptive atlas."""
+    dict(max_side=N, min_texels=, max_texels=) -> None, the checked texels, or the checked dict of the adaptive atlas.  With
+    images=dict(...) (_photo_options) in the dict the result is a dict in either case, dict(texels=T, images=...) for the uniform
+    atlas."""
     if texture is None:
         return None
     opts = dict(texture) if isinstance(texture, dict) else dict(texels=texture)
-    unknown = set(opts) - {"texels", "texel_size", "max_side", "min_texels", "max_texels"}
+    unknown = set(opts) - {"texels", "texel_size", "max_side", "min_texels", "max_texels", "images"}
     if unknown:
         raise ValueError("texture: unknown keys %r" % sorted(unknown))
+    if opts.get("images") is not None:                  # either atlas, its colours from photographs: the atlas's options with "images" added
+        photo = _photo_options(opts.pop("images"))
+        out = _texture_options(opts)
+        out = dict(out) if isinstance(out, dict) else dict(texels=out)
+        out["images"] = photo
+        return out
+    opts.pop("images", None)
     if "texel_size" in opts or "max_side" in opts:
         if "texels" in opts or ("texel_size" in opts and "max_side" in opts):
             raise ValueError("texture: texels, texel_size and max_side exclude each other: %r" % sorted(opts))
@@ -1535,11 +1724,13 @@ def _tsdf(model, resolution, lo, hi, K, poses, img_wh, trunc_voxels=4.0, min_opa
 
 
 def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None, simplify_voxels=None, tsdf=None,
-             smooth=None, texture=None, simplify_placement="mean", decimate=None):
+             smooth=None, texture=None, simplify_placement="mean", decimate=None, stats=None):
     """extract_mesh (with `texture`: baked after the simplification and the colours, before the smoothing), (components found, components kept) when a filter option is set (else None), the number of faces the cull
     dropped when `cull` is set (else None), (V0, V1, F0, F1) around the simplification when simplify_voxels is set (else None), and
     (pairs, the topology's totals (4,) i64 on the device or None) when `smooth` is set (else None).  With `decimate` the tuple of the
-    simplification covers the decimation too (the sizes before the first and after the last of the two)."""
+    simplification covers the decimation too (the sizes before the first and after the last of the two).  With `stats` a dict and
+    texture=dict(..., images=...), stats["texture_images"] gets the number of cameras and, as device sums, the numbers of valid texels
+    and of texels the photographs coloured."""
     smooth = _smooth_options(smooth)
     texture = _texture_options(texture)
     decimate = _decimate_options(decimate)
@@ -1587,14 +1778,29 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
     if colors:
         m.colors = vertex_colors(model, m.vertices, m.normals)
     baked = None
+    bake = lambda **atlas: bake_texture(model, m, **atlas).texture
+    if isinstance(texture, dict) and "images" in texture:   # colours from photographs, the field's where none sees the texel
+        texture = dict(texture)
+        photo = dict(texture.pop("images"))
+        if photo["bias"] is None:                        # two voxels of the coarsest axis, as the cull's
+            photo["bias"] = 2.0 * max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution)))
+        texture = texture["texels"] if "texels" in texture else texture
+
+        def bake(**atlas):
+            out, seen = bake_texture_from_images(m, model=model, return_seen=True, **photo, **atlas)
+            if stats is not None:                       # device sums: the caller reads them when it wants the share
+                with_normals = m if m.normals is not None else dataclasses.replace(m, normals=vertex_normals(m))
+                valid = texel_points(with_normals, out.texture, _box(model))[2]
+                stats["texture_images"] = dict(cameras=len(photo["poses"]), valid_texels=valid.sum(), seen_texels=seen.sum())
+            return out.texture
     if isinstance(texture, dict):                        # texel density by face size: texel_size in units of the largest lattice spacing
         if "max_side" in texture:
             size = fit_texel_size(m, texture["max_side"], texture["min_texels"], texture["max_texels"])
         else:
             size = texture["texel_size"] * max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution)))
-        baked = bake_texture(model, m, texel_size=size, min_texels=texture["min_texels"], max_texels=texture["max_texels"]).texture
+        baked = bake(texel_size=size, min_texels=texture["min_texels"], max_texels=texture["max_texels"])
     elif texture is not None:
-        baked = bake_texture(model, m, texture).texture
+        baked = bake(texels=texture)
     smoothed = None
     if smooth is not None:
         cell, _ = _grid(max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution))), None)
@@ -1630,6 +1836,10 @@ def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=Fals
     texel_size is given in units of the largest lattice spacing, as decimate's max_error is; texture=dict(max_side=N, ...) takes the
     texel_size that fit_texel_size finds for an atlas of at most N x N texels.  This is the atlas for a decimated mesh, whose faces
     differ in size.
+    images=dict(images=, K=, poses=, img_wh=, bias=None, guard=1, min_cos=0.1, power=2, min_views=1) inside either texture dict
+    takes the texels' colours from those photographs instead (bake_texture_from_images; bias=None is twice the largest lattice
+    spacing, as the cull's): at the same place, before the smoothing, on the geometry the photographs saw.  A texel that fewer than
+    min_views photographs see keeps the field's colour.
     decimate=N, or dict(target_faces=N, max_error=VOXELS), adds `decimate` after simplify_voxels and before the colours, the texture
     and the smoothing, which see the decimated mesh as they see the clustered one: cell is the largest lattice spacing and
     max_error is given in units of it.  Without it nothing new runs or loads."""
@@ -1811,6 +2021,18 @@ def main(argv=None):
                     help="as --texture-texel-size, with the smallest texel size found whose atlas is at most N x N texels")
     ap.add_argument("--texture-min-texels", type=int, default=None, metavar="T", help="fewest texels along a face's leg (a ladder value; default 1)")
     ap.add_argument("--texture-max-texels", type=int, default=None, metavar="T", help="most texels along a face's leg (a ladder value; default 256)")
+    ap.add_argument("--texture-images", default=None, metavar="FILE.npz",
+                    help="take the texels' colours from photographs instead of the field: an .npz with K (3, 3), poses (C, 3, 4) camera-to-world, "
+                         "img_wh (W, H) and images (C, H, W, 3) uint8; texels no photograph sees keep the field's colour; needs one of the "
+                         "--texture-* atlas options and an --out that ends in .obj; prints the share of texels seen as one JSON line")
+    ap.add_argument("--texture-image-bias", type=float, default=None, metavar="B",
+                    help="depth slack of the visibility test in world units (default: two voxels)")
+    ap.add_argument("--texture-image-guard", type=int, default=None, metavar="G",
+                    help="pixels round a texel's projection whose depths must agree with its own, 0..4 (default 1)")
+    ap.add_argument("--texture-image-min-cos", type=float, default=None, metavar="C",
+                    help="smallest cosine between the normal and the direction to a camera that still counts, in (0, 1] (default 0.1)")
+    ap.add_argument("--texture-image-power", type=int, default=None, metavar="P", help="a photograph's weight is that cosine to the power P, 1..8 (default 2)")
+    ap.add_argument("--texture-image-min-views", type=int, default=None, metavar="N", help="photographs a texel needs (default 1)")
     ap.add_argument("--score-cameras", default=None, metavar="FILE.npz",
                     help="score the textured mesh against the field's own renders from these cameras (PSNR, SSIM; compare_renders) and "
                          "print the record as one JSON line: an .npz as --cull-cameras takes; needs --texture-texels")
@@ -1870,6 +2092,24 @@ def main(argv=None):
         ap.error("an .obj output needs --texture-texels T (or --texture-texel-size VOXELS, --texture-max-side N)")
     if a.texture_texels is not None and not 1 <= a.texture_texels <= 256:
         ap.error("--texture-texels takes T in 1..256")
+    image_flags = (("--texture-image-bias", a.texture_image_bias), ("--texture-image-guard", a.texture_image_guard),
+                   ("--texture-image-min-cos", a.texture_image_min_cos), ("--texture-image-power", a.texture_image_power),
+                   ("--texture-image-min-views", a.texture_image_min_views))
+    if a.texture_images is None and any(x is not None for _, x in image_flags):
+        ap.error("%s need --texture-images" % ", ".join(flag for flag, _ in image_flags))
+    if a.texture_images is not None:
+        if texture_opts is None:
+            ap.error("--texture-images needs an atlas: one of --texture-texels, --texture-texel-size, --texture-max-side")
+        if not obj:
+            ap.error("--texture-images needs an --out that ends in .obj: a PLY carries no texture")
+        try:
+            _photo_args(0.0 if a.texture_image_bias is None else a.texture_image_bias,
+                        1 if a.texture_image_guard is None else a.texture_image_guard,
+                        0.1 if a.texture_image_min_cos is None else a.texture_image_min_cos,
+                        2 if a.texture_image_power is None else a.texture_image_power,
+                        1 if a.texture_image_min_views is None else a.texture_image_min_views, NEAR_DISTANCE)
+        except ValueError as e:
+            ap.error("--texture-image-*: %s" % e)
     if a.score_cameras is not None and texture_opts is None:
         ap.error("--score-cameras needs --texture-texels: the score is of the textured mesh")
     if a.score_out is not None and a.score_cameras is None:
@@ -1905,9 +2145,19 @@ def main(argv=None):
     decimate_opts = None
     if a.decimate_faces is not None or a.decimate_max_error is not None:
         decimate_opts = dict(target_faces=a.decimate_faces, max_error=a.decimate_max_error)
+    stats = {}
+    if a.texture_images is not None:
+        with np.load(a.texture_images) as photos:
+            photo = dict(images=photos["images"], K=photos["K"], poses=photos["poses"], img_wh=tuple(int(n) for n in photos["img_wh"]),
+                         bias=a.texture_image_bias)
+        for key, x in (("guard", a.texture_image_guard), ("min_cos", a.texture_image_min_cos), ("power", a.texture_image_power),
+                       ("min_views", a.texture_image_min_views)):
+            if x is not None:
+                photo[key] = x
+        texture_opts = dict(texture_opts if isinstance(texture_opts, dict) else dict(texels=texture_opts), images=photo)
     m, found, culled, simplified, smoothed = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull,
                                                       a.simplify_voxels, tsdf, smooth, texture_opts, a.simplify_placement or "mean",
-                                                      decimate_opts)
+                                                      decimate_opts, stats)
     if obj:
         save_obj(a.out, m)
     else:
@@ -1930,10 +2180,19 @@ def main(argv=None):
             line += ", texel size %.6g, faces per texels %s" % (
                 m.texture.texel_size, " ".join("%d:%d" % (t, n) for t, n in zip(_meshatlas_lib.LADDER, m.texture.counts) if n))
     print(line)
+    seen_record = None
+    if "texture_images" in stats:
+        import json
+        st = stats["texture_images"]
+        n_valid, n_seen = int(st["valid_texels"].item()), int(st["seen_texels"].item())
+        seen_record = dict(cameras=st["cameras"], valid_texels=n_valid, seen_texels=n_seen, seen_share=n_seen / n_valid if n_valid else 0.0)
+        print(json.dumps(dict(texture_images=seen_record)))
     if a.score_cameras is not None:
         import json
         with np.load(a.score_cameras) as cams:
             record = compare_renders(model, m, cams["K"], cams["poses"], tuple(int(n) for n in cams["img_wh"]))
+        if seen_record is not None:
+            record["texture_images"] = seen_record
         text = json.dumps(record)
         if a.score_out is not None:
             with open(a.score_out, "w") as f:
