@@ -153,14 +153,15 @@ def matmul_acc16(h, w):
     return acc
 
 
-def mlp(x, params, n_in, n_hidden, n_out, out_act="None", quantize=False, acc16=False):
+def mlp(x, params, n_in, n_hidden, n_out, out_act="None", quantize=False, acc16=False, dtype=torch.float32):
     """FullyFusedMLP: ReLU hidden, no bias.  Returns (S, n_out) PRE-rounding f32 (after out_act).
-    acc16 (forward only, implies quantize): f16 accumulators, see matmul_acc16."""
+    acc16 (forward only, implies quantize): f16 accumulators, see matmul_acc16.
+    dtype=torch.float64: the sums in float64 (tests/test_field_forward_reference_cpu.py)."""
     ws = split_mlp_params(params, n_in, n_hidden)
     quantize = quantize or acc16
-    h = q16(x.float()) if quantize else x.float()
+    h = q16(x.to(dtype)) if quantize else x.to(dtype)
     for i, w in enumerate(ws):
-        w = q16(w.float()) if quantize else w.float()
+        w = q16(w.to(dtype)) if quantize else w.to(dtype)
         h = matmul_acc16(h, w) if acc16 else h @ w.t()
         if i < len(ws) - 1:
             h = torch.relu(h)

@@ -209,10 +209,29 @@ def field_native(lib, field, x, d):
     return feats, sig, rgb, h, dw, rw, ds
 
 
+def assert_field_within_intervals(feats, d, dw, rw, h, sig, rgb):
+    """Every h inside its interval around the exact sums of the features, sigma against the kernel's own h[0], rgb inside the interval
+    propagated from the kernel's own h and an f16 value (tests/field_forward_reference.py: exact sums, e = K 2^-23 mass per layer,
+    monotone f16 rounding) -- next to, not instead of, the tolerances against the oracle."""
+    from tests import field_forward_reference as F
+    n = d.shape[0]
+    dws, rws = F.split_weights(dw.cpu().numpy(), 32, 1), F.split_weights(rw.cpu().numpy(), 32, 2)
+    ref = F.mlp_intervals(dws, feats.permute(1, 0, 2).reshape(n, 32).cpu().numpy())
+    hk = h.cpu().numpy()
+    res = F.check(hk, ref.lo, ref.hi, "h")
+    assert res.bad == 0, res.worst
+    res = F.check_sigma(sig.cpu().numpy(), hk[:, 0])
+    assert res.bad == 0, res.worst
+    lo, hi = F.colour_intervals(rws, d.numpy(), hk)
+    res = F.check_rgb(rgb.cpu().numpy(), lo, hi)
+    assert res.bad == 0, res.worst
+
+
 def test_field_forward(lib, field):
     for n in (1, 31, 32, 33, 4097, 50000):          # ragged tails around the 32-sample MFMA tile
         x, d = sample_points(n, seed=4)
-        feats, sig, rgb, h, *_ = field_native(lib, field, x, d)
+        feats, sig, rgb, h, dw, rw, _ = field_native(lib, field, x, d)
+        assert_field_within_intervals(feats, d, dw, rw, h, sig, rgb)
         ws, wr, wh = field.forward(x, d, quantize=True)
         # h: f16 output of a 64-wide dot product of f16 activations; 2 ulp of the largest |h| + summation noise
         hmax = wh.abs().max().item()
@@ -333,7 +352,12 @@ def test_generic_mlp(lib, n_in, n_hidden, n_out, act):
     wp = w.clone().requires_grad_(True); xp = x.float().requires_grad_(True)
     want = T.mlp(xp, wp, n_in, n_hidden, n_out, "Sigmoid" if act else "None", quantize=True)
     np.testing.assert_allclose(out.float().cpu().numpy(), want.detach().numpy(), rtol=3e-3, atol=3e-3 * max(1.0, want.abs().max().item()))
-    dout = (torch.randn(n, n_out, generator=g) * 0.1).half()
+    # ... and every output inside its own interval around the exact sums (tests/field_forward_reference.py)
+    from tests import field_forward_reference as F
+    ref = F.mlp_intervals(F.split_weights(w.half().numpy(), n_in, n_hidden), x.numpy())
+    res = F.check(out.cpu().numpy(), (ref.act_lo if act else ref.lo)[:, :n_out], (ref.act_hi if act else ref.hi)[:, :n_out], "ngp_mlp_fwd")
+    assert res.bad == 0, res.worst
+    dout =(torch.randn(n, n_out, generator=g) * 0.1).half()
     want.backward(dout.float())
     n_part = lib.call("ngp_mlp_bwd_partials", n)
     partials = torch.empty(n_part, w.numel(), device="cuda")
