@@ -33,6 +33,10 @@
   libngp_meshphoto.so -- the colour of surface points blended from photographs (projection, a two-sided depth test against the
                      mesh's depth buffers, a bilinear sample, a weight by viewing angle, serial per-point sums) behind
                      csrc/meshphoto/ngp_meshphoto.h, which lies beside its sources under csrc/meshphoto/.
+  libngp_meshnormal.so -- the normals of a detail mesh carried onto the texels of a simplified one (the nearest face that faces the
+                     same way, exactly the brute-force minimum through libngp_meshdist.so's grid; interpolated vertex normals) and
+                     the shading of a frame by a rendered normal map behind csrc/meshnormal/ngp_meshnormal.h, which lies beside
+                     its sources under csrc/meshnormal/.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -116,6 +120,11 @@ MESHPHOTO_SOURCES = [os.path.join("meshphoto", "meshphoto.hip")]
 MESHPHOTO_HEADERS = [os.path.join("meshphoto", "ngp_meshphoto.h")]
 # projection, the viewing angle, the depth test, the bilinear sample and the weighted sums are the plain f32 expressions of csrc/meshphoto/ngp_meshphoto.h, as tests/mesh_photo_reference.py has them
 MESHPHOTO_CFLAGS = ["-ffp-contract=off"]
+MESHNORMAL_LIB = os.path.join(CSRC, "libngp_meshnormal.so")
+MESHNORMAL_SOURCES = [os.path.join("meshnormal", "meshnormal.hip")]
+MESHNORMAL_HEADERS = [os.path.join("meshnormal", "ngp_meshnormal.h")]
+# the orientation test, the closest point of a triangle, the interpolated normal and the shading are the plain f32 expressions of csrc/meshnormal/ngp_meshnormal.h, as tests/mesh_normal_reference.py has them
+MESHNORMAL_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -159,8 +168,9 @@ def build(force=False, verbose=False):
     decimate_objs, decimate_jobs = _plan(MESHDECIMATE_SOURCES, MESHDECIMATE_HEADERS, lambda src: MESHDECIMATE_CFLAGS, force)
     atlas_objs, atlas_jobs = _plan(MESHATLAS_SOURCES, MESHATLAS_HEADERS, lambda src: MESHATLAS_CFLAGS, force)
     photo_objs, photo_jobs = _plan(MESHPHOTO_SOURCES, MESHPHOTO_HEADERS, lambda src: MESHPHOTO_CFLAGS, force)
+    normal_objs, normal_jobs = _plan(MESHNORMAL_SOURCES, MESHNORMAL_HEADERS, lambda src: MESHNORMAL_CFLAGS, force)
     todo = (jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs + dist_jobs
-            + quadric_jobs + decimate_jobs + atlas_jobs + photo_jobs)
+            + quadric_jobs + decimate_jobs + atlas_jobs + photo_jobs + normal_jobs)
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -172,7 +182,7 @@ def build(force=False, verbose=False):
                             (MESHTEX_LIB, tex_objs, tex_jobs), (METRICS_LIB, metrics_objs, metrics_jobs),
                             (MESHDIST_LIB, dist_objs, dist_jobs), (MESHQUADRIC_LIB, quadric_objs, quadric_jobs),
                             (MESHDECIMATE_LIB, decimate_objs, decimate_jobs), (MESHATLAS_LIB, atlas_objs, atlas_jobs),
-                            (MESHPHOTO_LIB, photo_objs, photo_jobs)):
+                            (MESHPHOTO_LIB, photo_objs, photo_jobs), (MESHNORMAL_LIB, normal_objs, normal_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

@@ -35,6 +35,10 @@
     c, ok, n = photo_colors(m, p, d, ok, images, K, poses, (W, H), bias=2 * voxel)               # colours blended from photographs (libngp_meshphoto.so)
     m = bake_texture_from_images(m, images, K, poses, (W, H), texels=8, bias=2 * voxel, model=model)   # the atlas from the photographs, the field where none sees
     m = extract_mesh(model, 512, decimate=200000, texture=dict(texel_size=1.0, images=dict(images=images, K=K, poses=poses, img_wh=(W, H))))
+    n, d, i, b = transfer_normals(p, -d, detail, max_dist=4 * voxel)   # the detail mesh's normals at the nearest face that faces the same way (libngp_meshnormal.so)
+    nm = bake_normal_map(m, detail, max_dist=4 * voxel)            # NormalMap: object-space normals of the detail mesh on m's atlas, (H, W, 3) u8
+    img = render_textured(m, K, poses, (W, H), normal_map=nm, light=(0.3, 0.5, 0.8))           # the textured mesh shaded by the normal map
+    m = extract_mesh(model, 512, decimate=200000, texture=dict(texel_size=1.0, normal_map=True))   # NormalMappedMesh: the detail from before the simplification
     r = compare_renders(model, m, K, poses, (W, H))                # PSNR and SSIM of the textured mesh's renders against the field's (libngp_metrics.so)
     p, w, i = sample_surface(m, spacing=voxel)                     # deterministic area samples: points, areas, face ids (libngp_meshdist.so)
     d, i = closest_on_mesh(p, m2)                                  # distance to and index of the nearest face of m2, exactly the brute-force minimum
@@ -42,6 +46,7 @@
     save_ply("mesh.ply", m)
     m = load_ply("mesh.ply", device="cuda")                        # what save_ply wrote, and nothing else
     save_obj("mesh.obj", m)                                        # mesh.obj + mesh.mtl + mesh.png (needs m.texture with an image)
+    save_obj("mesh.obj", m, normal_map=m.normal_map)               # and mesh_normal.png, named by a `norm` line of the MTL
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
                               [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]]
@@ -51,6 +56,7 @@
                               [--texture-texels T | --texture-texel-size VOXELS | --texture-max-side N [--texture-min-texels T] [--texture-max-texels T]
                                [--texture-images PHOTOS.npz [--texture-image-bias B] [--texture-image-guard G] [--texture-image-min-cos C]
                                 [--texture-image-power P] [--texture-image-min-views N]]
+                               [--texture-normal-map [--texture-normal-max-dist VOXELS] [--texture-normal-two-sided]]
                                [--score-cameras CAMS.npz [--score-out FILE.json]]]
                               [--distance-to REF.ply [--distance-spacing S] [--distance-thresholds T1,T2,...] [--distance-out FILE.json]]
                               --out mesh.ply | mesh.obj
@@ -77,6 +83,7 @@ from . import (_lib, _mesh_lib, _meshcull_lib, _meshdecimate_lib, _meshdist_lib,
                _meshsmooth_lib, _meshtex_lib, _meshtsdf_lib)
 from . import _meshatlas_lib                                      # binds libngp_meshatlas.so only when an AdaptiveTexture is asked for
 from . import _meshphoto_lib                                      # binds libngp_meshphoto.so only when a texture is baked from photographs
+from . import _meshnormal_lib                                     # binds libngp_meshnormal.so only when a normal map is asked for
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -90,6 +97,11 @@ class Mesh:
     normals: object = None      # (V, 3) f32, unit, outward (density falls outward); 0 where the gradient vanishes
     colors: object = None       # (V, 3) f32 RGB in [0, 1], or None
     texture: object = None      # Texture (atlas layout, per-face UVs, image), or None
+
+
+@dataclasses.dataclass
+class NormalMappedMesh(Mesh):
+    normal_map: object = None   # NormalMap: the normals of the mesh before its simplification, on this mesh's atlas
 
 
 def _resolution(resolution):
@@ -1252,13 +1264,72 @@ def bake_texture_from_images(mesh, images, K, poses, img_wh, texels=8, texel_siz
     return (out, seen_map.view(t.height, t.width)) if return_seen else out
 
 
-def render_textured(mesh, K, poses, img_wh, background=(1, 1, 1), near=NEAR_DISTANCE, max_workspace_bytes=1 << 28, return_ids=False):
+def _light(light):
+    """A world direction towards the light -> its three f32 components at unit length (ValueError for anything else)."""
+    try:
+        l = np.asarray([float(x) for x in light], np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("light must be three numbers, a world direction towards the light: %r" % (light,))
+    with np.errstate(all="ignore"):
+        length = np.sqrt((l[0] * l[0] + l[1] * l[1]) + l[2] * l[2]) if l.shape == (3,) else np.float32(0)
+    if l.shape != (3,) or not (np.isfinite(length) and length > 0):
+        raise ValueError("light must be three finite numbers, not all zero: %r" % (light,))
+    return l / length
+
+
+def _ambient(ambient):
+    if isinstance(ambient, bool) or not isinstance(ambient, (int, float, np.integer, np.floating)) or not 0 <= float(np.float32(ambient)) <= 1:
+        raise ValueError("ambient must be a number in [0, 1]: %r" % (ambient,))
+    return float(np.float32(ambient))
+
+
+def shade_with_normals(albedo, samples, ids, lights, ambient=0.25):
+    """albedo (C, H, W, 3) f32 shaded by the normals decoded from samples (C, H, W, 3) f32, a rendered normal-map image: per pixel
+    with ids (C, H, W) i32 >= 0, albedo * (ambient + (1 - ambient) * max(dot(n, light), 0)) with n = (2 s - 1) normalised and light
+    = lights[c] (C, 3) f32 on the device, unit, towards the light; factor 1 where 2 s - 1 has no direction; other pixels are
+    copied (csrc/meshnormal/ngp_meshnormal.h has the exact rule).  No host sync."""
+    ambient = _ambient(ambient)
+    for name, t, dt in (("albedo", albedo, torch.float32), ("samples", samples, torch.float32), ("ids", ids, torch.int32), ("lights", lights, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError("%s must be a %s tensor" % (name, dt))
+        _require_cuda(t, name)
+    if albedo.dim() != 4 or albedo.shape[3] != 3 or samples.shape != albedo.shape or tuple(ids.shape) != tuple(albedo.shape[:3]) \
+            or tuple(lights.shape) != (albedo.shape[0], 3):
+        raise ValueError("albedo and samples must be (C, H, W, 3), ids (C, H, W) and lights (C, 3): %r, %r, %r, %r"
+                         % (tuple(albedo.shape), tuple(samples.shape), tuple(ids.shape), tuple(lights.shape)))
+    albedo, samples, ids, lights = albedo.contiguous(), samples.contiguous(), ids.contiguous(), lights.contiguous()
+    out = torch.empty_like(albedo)
+    with device_guard(albedo.device):
+        _meshnormal_lib.call("ngp_meshnormal_shade", ptr(albedo), ptr(samples), ptr(ids), ptr(lights), albedo.shape[0], albedo.shape[1],
+                             albedo.shape[2], ambient, ptr(out), stream())
+    return out
+
+
+def render_textured(mesh, K, poses, img_wh, background=(1, 1, 1), near=NEAR_DISTANCE, max_workspace_bytes=1 << 28, return_ids=False,
+                    normal_map=None, light=None, ambient=0.25):
     """(C, H, W, 3) f32: the mesh with its baked texture seen from the cameras K (3, 3), poses (C, 3, 4) camera-to-world, img_wh =
     (W, H) -- NGP.mark_invisible_cells' arguments.  Per pixel the nearest face that covers its centre (the cull's rasteriser rule;
     at equal depth the smaller face index), its texture looked up bilinearly at the perspective-correct point; `background` where
     no face lands (include/ngp_meshtex.h has the exact rule).  The cameras go through a key buffer of 8 bytes per pixel, as many
     at a time as fit max_workspace_bytes (at least one); the result does not depend on that.  return_ids=True also returns the
-    face index (C, H, W) i32 (-1 for none) and the depth (C, H, W) f32 (+inf for none).  No host sync."""
+    face index (C, H, W) i32 (-1 for none) and the depth (C, H, W) f32 (+inf for none).  No host sync.
+    With normal_map (a NormalMap of this mesh's atlas, bake_normal_map) and light (a world direction towards the light) both set,
+    the frame is shaded: the normal map's image is rendered through the same renderer in place of the texture's, and every covered
+    pixel is multiplied by ambient + (1 - ambient) * max(dot(n, light), 0) with n the normal decoded from that render
+    (shade_with_normals).  With either left None the result is the unshaded frame, bit for bit."""
+    if normal_map is not None and light is not None:
+        if not isinstance(normal_map, NormalMap) or mesh.texture is None:
+            raise ValueError("normal_map must be a NormalMap (bake_normal_map) and the mesh must carry its texture")
+        img = normal_map.image
+        if (not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or tuple(img.shape) != (mesh.texture.height, mesh.texture.width, 3)):
+            raise ValueError("normal_map.image must be a (H, W, 3) uint8 tensor of the size of the mesh's atlas")
+        l, ambient = _light(light), _ambient(ambient)
+        albedo, ids, depth = render_textured(mesh, K, poses, img_wh, background, near, max_workspace_bytes, return_ids=True)
+        carrier = dataclasses.replace(mesh, texture=dataclasses.replace(mesh.texture, image=img))
+        samples = render_textured(carrier, K, poses, img_wh, background, near, max_workspace_bytes)
+        lights = torch.from_numpy(l).to(albedo.device).expand(albedo.shape[0], 3).contiguous()
+        image = shade_with_normals(albedo, samples, ids, lights, ambient)
+        return (image, ids, depth) if return_ids else image
     _cameras(K, poses, img_wh)
     v, f, _ = _check_mesh(mesh)
     adaptive = isinstance(mesh.texture, AdaptiveTexture)
@@ -1501,6 +1572,147 @@ def closest_on_mesh(points, mesh, cell=None, max_dist=None, return_points=False,
     return out
 
 
+@dataclasses.dataclass
+class NormalMap:
+    image: object               # (H, W, 3) u8, row 0 on top: round(255 * (n * 0.5 + 0.5)) of the object-space (world-axes) normal; 0 for invalid texels
+    width: int
+    height: int
+    max_dist: float             # the reach of the transfer, world units (as a float32 value)
+    oriented: bool              # only faces of the detail mesh that face the way the texel does were candidates
+    hits: object                # device scalar i64: valid texels that found a face
+    valid: object               # device scalar i64: valid texels
+
+
+def _max_dist(max_dist):
+    if isinstance(max_dist, bool) or not isinstance(max_dist, (int, float, np.integer, np.floating)):
+        raise ValueError("max_dist must be a finite number >= 0 (world units): %r" % (max_dist,))
+    with np.errstate(all="ignore"):
+        d = float(np.float32(max_dist))
+    if not (math.isfinite(d) and d >= 0):
+        raise ValueError("max_dist must be a finite number >= 0 (world units, as a float32): %r" % (max_dist,))
+    return d
+
+
+def _normal_grid(v, f, max_dist):
+    """The grid of a normal transfer: distance_grid's, its cell raised where needed so that max_dist <= 4 cells (the library takes
+    up to _meshnormal_lib.MAX_SHELLS = 8).  Two host reads."""
+    extent = _mesh_extent(v, f).tolist()
+    mean = extent[6]
+    cell = 2.0 * mean if math.isfinite(mean) and mean > 0 else 1.0
+    origin, cell, dims = _plan_grid(extent, max(cell, max_dist / 4.0))
+    return _build_grid(v, f, origin, cell, dims)
+
+
+def _transfer(points, normals, valid, v, f, vn, grid, max_dist, oriented, want_bary=True, debug=False, out=None):
+    """ngp_meshnormal_transfer -> normals (N, 3) f32, d2 (N,) f32, face (N,) i32, bary (N, 2) f32 or None, debug (N, 2) i32 or None.
+    No host sync."""
+    n, dev = points.shape[0], points.device
+    if out is None:
+        out = (torch.empty(n, 3, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+               torch.empty(n, dtype=torch.int32, device=dev))
+    bary = torch.empty(n, 2, dtype=torch.float32, device=dev) if want_bary else None
+    dbg = torch.empty(n, 2, dtype=torch.int32, device=dev) if debug else None
+    with device_guard(dev):
+        _meshnormal_lib.call("ngp_meshnormal_transfer", ptr(points), ptr(normals), ptr(valid), n, ptr(v), ptr(f), ptr(vn), v.shape[0],
+                             f.shape[0], _meshnormal_lib.floats(grid.origin), grid.cell, grid.dims[0], grid.dims[1], grid.dims[2],
+                             ptr(grid.workspace), grid.workspace.numel() * 8, ptr(grid.entries), grid.n_entries, max_dist,
+                             1 if oriented else 0, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(bary), ptr(dbg), stream())
+    return out[0], out[1], out[2], bary, dbg
+
+
+def _detail(detail):
+    """-> (v, f, vertex normals) of the detail mesh: its own normals, or vertex_normals(detail) where it has none."""
+    v, f, extra = _check_mesh(detail)
+    vn = extra[0] if extra[0] is not None else (_normals(v, f) if v.shape[0] else torch.empty_like(v))
+    return v, f, vn.contiguous()
+
+
+def transfer_normals(points, normals, detail, max_dist, oriented=True, grid=None, return_debug=False, valid=None):
+    """For every point of points (N, 3) f32 with its own normal normals (N, 3) f32: the normal of `detail` at the point of its
+    surface nearest to the query, where with oriented=True only the faces that face the way the query's normal does are candidates
+    (dot(face normal, query normal) > 0) -- at a thin wall the plain nearest face can be the sheet that faces the other way.
+    Returns (normals (N, 3) f32 unit, distance (N,) f32, face (N,) i32, bary (N, 2) f32): the detail's vertex normals (its .normals,
+    or vertex_normals(detail) where None) interpolated at the closest point and normalised, the distance, the face of the detail
+    mesh and the barycentric pair (v, w) of the closest point.  A query that finds no candidate within max_dist (finite, world
+    units) is a miss: distance +inf, face -1, and its own normal normalised ((0, 0, 1) where it has no direction) as the normal.
+    csrc/meshnormal/ngp_meshnormal.h has the exact rule; the result is the brute-force minimum bit for bit, whatever the grid.
+    grid=distance_grid(detail) reuses a grid, whose cell must be at least max_dist / 8; without it one is built with max_dist <= 4
+    cells (two host reads), with it there is no host read.  valid (N,) u8 marks the queries to answer (default: all); the others
+    get normal 0, distance +inf, face -1.  return_debug=True appends (N, 2) i32: the shells visited and the faces evaluated.
+    A point whose largest |coordinate| is above (2^14 + 8) cells of the grid is answered as a query that is not valid (a device
+    mask, no host read).  The grid's own coordinates are at most 2^14 cells, so such a point lies more than 8 cells, the largest
+    max_dist, outside the grid, and with a grid that covers the detail mesh it has no face within reach; its slack, which grows
+    with its magnitude, would otherwise keep the max_dist exit from ending a walk that finds no candidate.  Every other point's
+    walk ends after shell 9 at the latest."""
+    v, f, vn = _detail(detail)
+    points = _check_points(points, v)
+    if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or tuple(normals.shape) != tuple(points.shape):
+        raise ValueError("normals must be a (N, 3) float32 tensor, one per point")
+    _require_cuda(normals, "normals")
+    if valid is None:
+        valid = torch.ones(points.shape[0], dtype=torch.uint8, device=points.device)
+    elif not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8 or tuple(valid.shape) != (points.shape[0],) or valid.device != points.device:
+        raise ValueError("valid must be a (N,) uint8 tensor on the points' device")
+    max_dist = _max_dist(max_dist)
+    if grid is None:
+        grid = _normal_grid(v, f, max_dist)
+    reach = (2.0 ** 14 + _meshnormal_lib.MAX_SHELLS) * grid.cell
+    valid = valid * (points.abs().amax(1) <= reach).to(torch.uint8) if points.shape[0] else valid        # NaN compares false: not valid either way
+    n, d2, face, bary, dbg = _transfer(points, normals.contiguous(), valid.contiguous(), v, f, vn, grid, max_dist, bool(oriented),
+                                       debug=return_debug)
+    return (n, d2.sqrt(), face, bary) + ((dbg,) if return_debug else ())
+
+
+@torch.no_grad()
+def bake_normal_map(mesh, detail, max_dist, oriented=True, chunk=1 << 20, box=None):
+    """NormalMap of `mesh` (which needs a .texture, either atlas; its image is not used): for every texel of the atlas the normal
+    of `detail` -- the mesh before its simplification -- transferred by transfer_normals from the texel's point with the texel's
+    own normal (texel_points: minus its direction), `chunk` texels at a time against one grid.  The image stores
+    round(clamp(n * 0.5 + 0.5, 0, 1) * 255), halves to even, 0 for invalid texels: an OBJECT-SPACE map in world axes.  A texel that
+    finds no face within max_dist (world units) keeps the simplified mesh's own interpolated normal.  box = (lo3, hi3) clamps the
+    texel points as bake_texture's does (default: the two meshes' bounding box).  If mesh.normals is None the texels' normals come
+    from vertex_normals(mesh).  The result is bit-identical run to run and for any chunk."""
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError("chunk must be an int >= 1: %r" % (chunk,))
+    max_dist = _max_dist(max_dist)
+    t = mesh.texture
+    if not isinstance(t, (Texture, AdaptiveTexture)):
+        raise ValueError("bake_normal_map needs mesh.texture (texture_atlas, bake_texture): %r" % (t,))
+    v, f, extra = _check_mesh(mesh)
+    if isinstance(t, AdaptiveTexture):
+        _check_adaptive(t, f.shape[0], v.device)
+    else:
+        _check_texture(t, f.shape[0])
+    dv, df, dvn = _detail(detail)
+    if dv.device != v.device:
+        raise ValueError("the detail mesh is on %s, the mesh on %s" % (dv.device, v.device))
+    normals = extra[0] if extra[0] is not None else _normals(v, f)
+    if box is None:                                      # one host read: both meshes' extents
+        e = torch.stack([_mesh_extent(v, f), _mesh_extent(dv, df)]).tolist()
+        lo = [min(a, b) for a, b in zip(e[0][:3], e[1][:3])]
+        hi = [max(a, b) for a, b in zip(e[0][3:6], e[1][3:6])]
+        box = (lo, hi) if all(math.isfinite(x) for x in lo + hi) else ((0, 0, 0), (0, 0, 0))
+    b6 = _box6(box)
+    grid = _normal_grid(dv, df, max_dist)
+    n = t.width * t.height
+    dev = v.device
+    image = torch.empty(n, 3, dtype=torch.uint8, device=dev)
+    hits = torch.zeros((), dtype=torch.int64, device=dev)
+    n_valid = torch.zeros((), dtype=torch.int64, device=dev)
+    chunk = int(min(chunk, n))
+    buf = out = None
+    for begin in range(0, n, chunk):
+        cnt = min(chunk, n - begin)
+        if buf is not None and buf[0].shape[0] != cnt:   # the last, shorter chunk
+            buf = out = None
+        buf = p, d, ok = _texel_points(v, f, normals, t, b6, begin, cnt, buf)
+        out = nrm, _, face = _transfer(p, -d, ok, dv, df, dvn, grid, max_dist, bool(oriented), want_bary=False, out=out)[:3]
+        image[begin:begin + cnt] = _quantise(nrm * 0.5 + 0.5) * ok.unsqueeze(1)
+        hits += ((face >= 0) & (ok != 0)).sum()
+        n_valid += (ok != 0).sum()
+    return NormalMap(image.view(t.height, t.width, 3), t.width, t.height, max_dist, bool(oriented), hits, n_valid)
+
+
 def _spacing(spacing):
     spacing = C.c_float(float(spacing)).value
     if not (math.isfinite(spacing) and spacing > 0):
@@ -1652,6 +1864,28 @@ def _photo_options(images):
     return out
 
 
+def _normal_options(normal_map):
+    """The `normal_map` entry of extract_mesh's `texture`: True or dict(max_dist=VOXELS, oriented=True) -> the checked dict, both
+    keys present (max_dist=None: max(4, 2 * simplify_voxels) lattice spacings, set by the caller)."""
+    if normal_map is True:
+        return dict(max_dist=None, oriented=True)
+    if not isinstance(normal_map, dict):
+        raise ValueError("texture: normal_map must be True or a dict(max_dist=VOXELS, oriented=True): %r" % (normal_map,))
+    unknown = set(normal_map) - {"max_dist", "oriented"}
+    if unknown:
+        raise ValueError("texture: normal_map: unknown keys %r" % sorted(unknown))
+    max_dist, oriented = normal_map.get("max_dist"), normal_map.get("oriented", True)
+    try:
+        ok = max_dist is None or _max_dist(max_dist) > 0
+    except ValueError:
+        ok = False
+    if not ok:
+        raise ValueError("texture: normal_map: max_dist must be a finite number of voxels > 0: %r" % (max_dist,))
+    if not isinstance(oriented, (bool, np.bool_)):
+        raise ValueError("texture: normal_map: oriented must be a bool: %r" % (oriented,))
+    return dict(max_dist=None if max_dist is None else _max_dist(max_dist), oriented=bool(oriented))
+
+
 def _texture_options(texture):
     """extract_mesh's `texture`: None, an int (texels), dict(texels=), dict(texel_size=VOXELS, min_texels=, max_texels=) or
     dict(max_side=N, min_texels=, max_texels=) -> None, the checked texels, or the checked dict of the adaptive atlas.  With
@@ -1660,9 +1894,16 @@ def _texture_options(texture):
     if texture is None:
         return None
     opts = dict(texture) if isinstance(texture, dict) else dict(texels=texture)
-    unknown = set(opts) - {"texels", "texel_size", "max_side", "min_texels", "max_texels", "images"}
+    unknown = set(opts) - {"texels", "texel_size", "max_side", "min_texels", "max_texels", "images", "normal_map"}
     if unknown:
         raise ValueError("texture: unknown keys %r" % sorted(unknown))
+    if opts.get("normal_map") not in (None, False):     # either atlas with a normal map: the atlas's options with "normal_map" added
+        normal = _normal_options(opts.pop("normal_map"))
+        out = _texture_options(opts)
+        out = dict(out) if isinstance(out, dict) else dict(texels=out)
+        out["normal_map"] = normal
+        return out
+    opts.pop("normal_map", None)
     if opts.get("images") is not None:                  # either atlas, its colours from photographs: the atlas's options with "images" added
         photo = _photo_options(opts.pop("images"))
         out = _texture_options(opts)
@@ -1730,7 +1971,8 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
     (pairs, the topology's totals (4,) i64 on the device or None) when `smooth` is set (else None).  With `decimate` the tuple of the
     simplification covers the decimation too (the sizes before the first and after the last of the two).  With `stats` a dict and
     texture=dict(..., images=...), stats["texture_images"] gets the number of cameras and, as device sums, the numbers of valid texels
-    and of texels the photographs coloured."""
+    and of texels the photographs coloured; with texture=dict(..., normal_map=...), stats["texture_normal_map"] gets the NormalMap
+    itself (its hits and valid are device counts), which main() hands to save_obj and reads for its JSON line."""
     smooth = _smooth_options(smooth)
     texture = _texture_options(texture)
     decimate = _decimate_options(decimate)
@@ -1739,6 +1981,13 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
     simplify_placement = _placement(simplify_placement, "simplify_placement")
     if simplify_placement != "mean" and simplify_voxels is None:
         raise ValueError("simplify_placement=%r needs simplify_voxels: there is nothing to place" % (simplify_placement,))
+    normal = None
+    if isinstance(texture, dict) and "normal_map" in texture:
+        texture = dict(texture)
+        normal = texture.pop("normal_map")
+        texture = texture["texels"] if set(texture) == {"texels"} else texture
+        if simplify_voxels is None and decimate is None:
+            raise ValueError("texture: normal_map carries the normals across a simplification: it needs simplify_voxels or decimate")
     lo, hi = _bounds(model, bounds)
     if tsdf is None:
         vol = density_volume(model, resolution, (lo, hi))
@@ -1763,6 +2012,7 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
         m = cull_invisible(m, bias=bias, **opts)
         culled = n_f - m.faces.shape[0]
     simplified = None
+    detail = m if normal is not None else None           # the mesh as it stands before the stages that throw detail away
     if simplify_voxels is not None:
         cell = float(simplify_voxels) * max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution)))
         before = (m.vertices.shape[0], m.faces.shape[0])
@@ -1801,6 +2051,14 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
         baked = bake(texel_size=size, min_texels=texture["min_texels"], max_texels=texture["max_texels"])
     elif texture is not None:
         baked = bake(texels=texture)
+    normal_map = None
+    if normal is not None:                               # where the texture is baked: before the smoothing
+        voxel = max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution)))
+        reach = normal["max_dist"] if normal["max_dist"] is not None else max(4.0, 2.0 * float(simplify_voxels or 0.0))
+        normal_map = bake_normal_map(dataclasses.replace(m, texture=baked), detail, reach * voxel, normal["oriented"], box=_box(model))
+        if stats is not None:
+            stats["texture_normal_map"] = normal_map
+    del detail
     smoothed = None
     if smooth is not None:
         cell, _ = _grid(max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution))), None)
@@ -1809,6 +2067,8 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
         smoothed = (smooth["iterations"], totals)
     if baked is not None:
         m.texture = baked
+    if normal_map is not None:
+        m = NormalMappedMesh(m.vertices, m.faces, m.normals, m.colors, m.texture, normal_map)
     return m, found, culled, simplified, smoothed
 
 
@@ -1842,7 +2102,12 @@ def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=Fals
     min_views photographs see keeps the field's colour.
     decimate=N, or dict(target_faces=N, max_error=VOXELS), adds `decimate` after simplify_voxels and before the colours, the texture
     and the smoothing, which see the decimated mesh as they see the clustered one: cell is the largest lattice spacing and
-    max_error is given in units of it.  Without it nothing new runs or loads."""
+    max_error is given in units of it.  Without it nothing new runs or loads.
+    normal_map=True, or dict(max_dist=VOXELS, oriented=True), inside either texture dict also bakes a normal map (bake_normal_map):
+    the detail mesh is the mesh as it stands just before simplify_voxels / decimate (after the filter and the cull), one of which
+    must run; the map is baked where the texture is, before the smoothing; max_dist is given in lattice spacings and defaults to
+    max(4, 2 * simplify_voxels), clustering moving a vertex by at most sqrt(3) * simplify_voxels.  The result is then a
+    NormalMappedMesh, a Mesh with one more field, normal_map.  Without it nothing new runs or loads."""
     return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels, tsdf, smooth,
                     texture, simplify_placement, decimate)[0]
 
@@ -1943,14 +2208,21 @@ def _png(image):
             + chunk(b"IEND", b""))
 
 
-def save_obj(path, m):
+def save_obj(path, m, normal_map=None):
     """Wavefront OBJ with its material and texture: `path`, and beside it the same name with .mtl and .png.  v per vertex, vn per
     vertex when normals exist, vt three per face (m.texture.uvs), f v/vt/vn (v/vt without normals) one-based, mtllib, usemtl, and
     map_Kd naming the PNG (8-bit RGB, m.texture.image).  Floats are written with 9 significant digits: they read back to the same
-    float32.  Standard library and numpy only."""
+    float32.  Standard library and numpy only.  With normal_map (a NormalMap of the mesh's atlas) NAME_normal.png is written too and
+    the MTL names it on a `norm` line, with a comment that the map is object-space; map_Bump is not written, since viewers read
+    that as a tangent-space or a height map."""
     t = m.texture
     if t is None or t.image is None:
         raise ValueError("save_obj needs a baked texture: mesh.texture with an image (bake_texture, extract_mesh(texture=T))")
+    normal_image = None
+    if normal_map is not None:
+        normal_image = np.ascontiguousarray(_np(normal_map.image), np.uint8)
+        if normal_image.shape != (t.height, t.width, 3):
+            raise ValueError("the normal map does not belong to this mesh's atlas: image %r, atlas %d x %d" % (normal_image.shape, t.width, t.height))
     v = _np(m.vertices).astype(np.float32).reshape(-1, 3)
     f = _np(m.faces).astype(np.int64).reshape(-1, 3)
     uv = _np(t.uvs).astype(np.float32).reshape(-1, 2)
@@ -1973,8 +2245,14 @@ def save_obj(path, m):
         out.write("\n".join(lines) + "\n")
     with open(stem + ".mtl", "w") as out:
         out.write("newmtl %s\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s.png\n" % (name, name))
+        if normal_image is not None:
+            out.write("# norm: an object-space normal map in world axes, rgb = normal * 0.5 + 0.5 (not tangent-space, not a height map)\n"
+                      "norm %s_normal.png\n" % name)
     with open(stem + ".png", "wb") as out:
         out.write(_png(image))
+    if normal_image is not None:
+        with open(stem + "_normal.png", "wb") as out:
+            out.write(_png(normal_image))
 
 
 def main(argv=None):
@@ -2033,6 +2311,14 @@ def main(argv=None):
                     help="smallest cosine between the normal and the direction to a camera that still counts, in (0, 1] (default 0.1)")
     ap.add_argument("--texture-image-power", type=int, default=None, metavar="P", help="a photograph's weight is that cosine to the power P, 1..8 (default 2)")
     ap.add_argument("--texture-image-min-views", type=int, default=None, metavar="N", help="photographs a texel needs (default 1)")
+    ap.add_argument("--texture-normal-map", action="store_true",
+                    help="also bake an object-space normal map from the mesh as it stands before --simplify-voxels / --decimate-* (one of "
+                         "which is needed) onto the atlas: NAME_normal.png, named by a `norm` line of the MTL; needs one of the --texture-* "
+                         "atlas options and an --out that ends in .obj; prints the share of texels that found a face as one JSON line")
+    ap.add_argument("--texture-normal-max-dist", type=float, default=None, metavar="VOXELS",
+                    help="how far from a texel the detailed mesh is searched, in voxels (default: max(4, 2 * --simplify-voxels))")
+    ap.add_argument("--texture-normal-two-sided", action="store_true",
+                    help="take the nearest face of the detailed mesh whichever way it faces (default: only faces that face the way the texel does)")
     ap.add_argument("--score-cameras", default=None, metavar="FILE.npz",
                     help="score the textured mesh against the field's own renders from these cameras (PSNR, SSIM; compare_renders) and "
                          "print the record as one JSON line: an .npz as --cull-cameras takes; needs --texture-texels")
@@ -2110,6 +2396,17 @@ def main(argv=None):
                         1 if a.texture_image_min_views is None else a.texture_image_min_views, NEAR_DISTANCE)
         except ValueError as e:
             ap.error("--texture-image-*: %s" % e)
+    if not a.texture_normal_map and (a.texture_normal_max_dist is not None or a.texture_normal_two_sided):
+        ap.error("--texture-normal-max-dist and --texture-normal-two-sided need --texture-normal-map")
+    if a.texture_normal_map:
+        if texture_opts is None:
+            ap.error("--texture-normal-map needs an atlas: one of --texture-texels, --texture-texel-size, --texture-max-side")
+        if not obj:
+            ap.error("--texture-normal-map needs an --out that ends in .obj: a PLY carries no texture")
+        if a.simplify_voxels is None and a.decimate_faces is None and a.decimate_max_error is None:
+            ap.error("--texture-normal-map carries normals across a simplification: it needs --simplify-voxels or --decimate-*")
+        if a.texture_normal_max_dist is not None and not (math.isfinite(a.texture_normal_max_dist) and a.texture_normal_max_dist > 0):
+            ap.error("--texture-normal-max-dist takes VOXELS > 0")
     if a.score_cameras is not None and texture_opts is None:
         ap.error("--score-cameras needs --texture-texels: the score is of the textured mesh")
     if a.score_out is not None and a.score_cameras is None:
@@ -2155,11 +2452,14 @@ def main(argv=None):
             if x is not None:
                 photo[key] = x
         texture_opts = dict(texture_opts if isinstance(texture_opts, dict) else dict(texels=texture_opts), images=photo)
+    if a.texture_normal_map:
+        texture_opts = dict(texture_opts if isinstance(texture_opts, dict) else dict(texels=texture_opts),
+                            normal_map=dict(max_dist=a.texture_normal_max_dist, oriented=not a.texture_normal_two_sided))
     m, found, culled, simplified, smoothed = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull,
                                                       a.simplify_voxels, tsdf, smooth, texture_opts, a.simplify_placement or "mean",
                                                       decimate_opts, stats)
     if obj:
-        save_obj(a.out, m)
+        save_obj(a.out, m, normal_map=stats.get("texture_normal_map"))
     else:
         save_ply(a.out, m)
     line = "%s: %d vertices, %d faces" % (a.out, m.vertices.shape[0], m.faces.shape[0])
@@ -2187,6 +2487,12 @@ def main(argv=None):
         n_valid, n_seen = int(st["valid_texels"].item()), int(st["seen_texels"].item())
         seen_record = dict(cameras=st["cameras"], valid_texels=n_valid, seen_texels=n_seen, seen_share=n_seen / n_valid if n_valid else 0.0)
         print(json.dumps(dict(texture_images=seen_record)))
+    if "texture_normal_map" in stats:
+        import json
+        nm = stats["texture_normal_map"]
+        n_valid, n_hit = int(nm.valid.item()), int(nm.hits.item())
+        print(json.dumps(dict(texture_normal_map=dict(valid_texels=n_valid, hit_texels=n_hit, hit_share=n_hit / n_valid if n_valid else 0.0,
+                                                      max_dist=nm.max_dist, oriented=nm.oriented, width=nm.width, height=nm.height))))
     if a.score_cameras is not None:
         import json
         with np.load(a.score_cameras) as cams:
