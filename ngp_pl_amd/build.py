@@ -8,7 +8,8 @@
                      sources live under csrc/meshfilter/.
   libngp_meshcull.so -- depth-buffer visibility of a mesh against cameras and the cull of unseen faces behind
                      include/ngp_meshcull.h; its sources live under csrc/meshcull/.  The order-preserving compaction
-                     (csrc/mesh_compact.h) is shared source of this library, the component filter and the simplifier.
+                     (csrc/mesh_compact.h) is shared source of this library, the component filter, the simplifier and the
+                     decimator.
   libngp_meshsimplify.so -- simplification of a mesh by vertex clustering behind include/ngp_meshsimplify.h; its sources
                      live under csrc/meshsimplify/.
   libngp_meshtsdf.so -- fusion of per-camera depth maps into a truncated signed distance volume on the export lattice behind
@@ -67,7 +68,7 @@ MESHFILTER_SOURCES = [os.path.join("meshfilter", "meshfilter.hip")]
 MESHFILTER_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshfilter.h")]
 MESHCULL_LIB = os.path.join(CSRC, "libngp_meshcull.so")
 MESHCULL_SOURCES = [os.path.join("meshcull", "meshcull.hip")]
-MESHCULL_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshcull.h")]
+MESHCULL_HEADERS = ["mesh_compact.h", "mesh_camera.h", "mesh_raster.h", os.path.join("..", "..", "include", "ngp_meshcull.h")]
 # projection, edge functions and depths are the plain f32 expressions of include/ngp_meshcull.h, as tests/mesh_visibility_reference.py has them
 MESHCULL_CFLAGS = ["-ffp-contract=off"]
 MESHSIMPLIFY_LIB = os.path.join(CSRC, "libngp_meshsimplify.so")
@@ -77,7 +78,7 @@ MESHSIMPLIFY_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "n
 MESHSIMPLIFY_CFLAGS = ["-ffp-contract=off"]
 MESHTSDF_LIB = os.path.join(CSRC, "libngp_meshtsdf.so")
 MESHTSDF_SOURCES = [os.path.join("meshtsdf", "meshtsdf.hip")]
-MESHTSDF_HEADERS = [os.path.join("..", "..", "include", "ngp_meshtsdf.h")]
+MESHTSDF_HEADERS = ["mesh_camera.h", os.path.join("..", "..", "include", "ngp_meshtsdf.h")]
 # lattice points, projection and truncated distances are the plain f32 expressions of include/ngp_meshtsdf.h, as tests/mesh_tsdf_reference.py has them
 MESHTSDF_CFLAGS = ["-ffp-contract=off"]
 MESHSMOOTH_LIB = os.path.join(CSRC, "libngp_meshsmooth.so")
@@ -87,7 +88,7 @@ MESHSMOOTH_HEADERS = [os.path.join("..", "..", "include", "ngp_meshsmooth.h")]
 MESHSMOOTH_CFLAGS = ["-ffp-contract=off"]
 MESHTEX_LIB = os.path.join(CSRC, "libngp_meshtex.so")
 MESHTEX_SOURCES = [os.path.join("meshtex", "meshtex.hip")]
-MESHTEX_HEADERS = [os.path.join("..", "..", "include", "ngp_meshtex.h")]
+MESHTEX_HEADERS = ["mesh_camera.h", "mesh_raster.h", os.path.join("..", "..", "include", "ngp_meshtex.h")]
 # texel points, directions, projection, barycentric weights and the bilinear lookup are the plain f32 expressions of include/ngp_meshtex.h, as tests/mesh_texture_reference.py has them
 MESHTEX_CFLAGS = ["-ffp-contract=off"]
 METRICS_LIB = os.path.join(CSRC, "libngp_metrics.so")
@@ -97,7 +98,7 @@ METRICS_HEADERS = [os.path.join("..", "..", "include", "ngp_metrics.h")]
 METRICS_CFLAGS = ["-ffp-contract=off"]
 MESHDIST_LIB = os.path.join(CSRC, "libngp_meshdist.so")
 MESHDIST_SOURCES = [os.path.join("meshdist", "meshdist.hip")]
-MESHDIST_HEADERS = [os.path.join("..", "..", "include", "ngp_meshdist.h")]
+MESHDIST_HEADERS = ["mesh_nearest.h", os.path.join("..", "..", "include", "ngp_meshdist.h")]
 # samples, the closest point of a triangle and the squared distance are the plain f32 expressions of include/ngp_meshdist.h, as tests/mesh_distance_reference.py has them
 MESHDIST_CFLAGS = ["-ffp-contract=off"]
 MESHQUADRIC_LIB = os.path.join(CSRC, "libngp_meshquadric.so")
@@ -112,17 +113,17 @@ MESHDECIMATE_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "n
 MESHDECIMATE_CFLAGS = ["-ffp-contract=off"]
 MESHATLAS_LIB = os.path.join(CSRC, "libngp_meshatlas.so")
 MESHATLAS_SOURCES = [os.path.join("meshatlas", "meshatlas.hip")]
-MESHATLAS_HEADERS = [os.path.join("meshatlas", "ngp_meshatlas.h")]
+MESHATLAS_HEADERS = ["mesh_camera.h", "mesh_raster.h", os.path.join("meshatlas", "ngp_meshatlas.h")]
 # edge lengths, class thresholds, texel points, projection, barycentric weights and the bilinear lookup are the plain f32 expressions of csrc/meshatlas/ngp_meshatlas.h, as tests/mesh_atlas_reference.py has them
 MESHATLAS_CFLAGS = ["-ffp-contract=off"]
 MESHPHOTO_LIB = os.path.join(CSRC, "libngp_meshphoto.so")
 MESHPHOTO_SOURCES = [os.path.join("meshphoto", "meshphoto.hip")]
-MESHPHOTO_HEADERS = [os.path.join("meshphoto", "ngp_meshphoto.h")]
+MESHPHOTO_HEADERS = ["mesh_camera.h", os.path.join("meshphoto", "ngp_meshphoto.h")]
 # projection, the viewing angle, the depth test, the bilinear sample and the weighted sums are the plain f32 expressions of csrc/meshphoto/ngp_meshphoto.h, as tests/mesh_photo_reference.py has them
 MESHPHOTO_CFLAGS = ["-ffp-contract=off"]
 MESHNORMAL_LIB = os.path.join(CSRC, "libngp_meshnormal.so")
 MESHNORMAL_SOURCES = [os.path.join("meshnormal", "meshnormal.hip")]
-MESHNORMAL_HEADERS = [os.path.join("meshnormal", "ngp_meshnormal.h")]
+MESHNORMAL_HEADERS = ["mesh_nearest.h", os.path.join("meshnormal", "ngp_meshnormal.h")]
 # the orientation test, the closest point of a triangle, the interpolated normal and the shading are the plain f32 expressions of csrc/meshnormal/ngp_meshnormal.h, as tests/mesh_normal_reference.py has them
 MESHNORMAL_CFLAGS = ["-ffp-contract=off"]
 

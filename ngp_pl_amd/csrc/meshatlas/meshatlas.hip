@@ -1,6 +1,7 @@
 // libngp_meshatlas.so: a texture atlas whose texel density follows the size of every face, and a renderer of the mesh textured that
 // way (C ABI and the exact rule: ngp_meshatlas.h beside this file).  Compiled with -ffp-contract=off: every f32 expression below is the
-// header's, operation by operation.  Nothing here is shared with csrc/meshtex/: the raster is this library's own.
+// header's, operation by operation.  No ABI header or source of csrc/meshtex/ is compiled in: the two renderers share only the
+// device code of ../mesh_camera.h and ../mesh_raster.h.
 //
 //   Classify, a stable counting sort of one digit with 16 buckets, blocks of BLOCK_FACES consecutive faces:
 //   atlas_count    the class of every face (three squared edge lengths, at most 16 compares) and the block's histogram: one ballot
@@ -15,11 +16,10 @@
 //                  vertices and normals; consecutive texels of a row share one or two faces.
 //   atlas_uvs      one thread per face: six f64 expressions.
 //   Render, per chunk of as many cameras as the caller's workspace holds, on the caller's stream: the keys cleared to all ones,
-//   atlas_raster   one work item per (face, camera), the cameras of a launch in LDS; a small pixel box is walked by the face's own
-//                  lane, larger ones are collected with a ballot and walked by the whole wave as an 8 x 8 tile; a 64-bit atomic
-//                  minimum of (depth bits, face), skipped when the pixel already holds a smaller key;
-//   atlas_shade    one thread per pixel: the winning face re-projected, its T, origin and slot from face_place, the bilinear
-//                  lookup with the four texels clamped into the atlas.
+//   atlas_raster   the shared rasteriser of ../mesh_raster.h with the sink KeySink: a 64-bit atomic minimum of (depth bits, face),
+//                  skipped when the pixel already holds a smaller key;
+//   atlas_shade    one thread per pixel: the winning face re-projected (../mesh_raster.h), its T, origin and slot from face_place,
+//                  the bilinear lookup of ../mesh_raster.h with the four texels clamped into the atlas.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -36,8 +36,6 @@ constexpr int ITERS = 8;
 constexpr int BLOCK_FACES = THREADS * ITERS;            // 2048
 constexpr int SCAN_THREADS = 1024;
 constexpr int NC = NGP_MESHATLAS_CLASSES;
-constexpr int CAM_TILE = 128;                           // cameras per launch: 12 floats each in LDS
-constexpr int SMALL_BOX = 64;                           // pixels a lane walks on its own
 constexpr int MAX_WH = 16384;
 constexpr float INF = __builtin_inff();
 constexpr unsigned long long NO_KEY = ~0ull;
@@ -394,140 +392,14 @@ __global__ __launch_bounds__(THREADS) void atlas_uvs(const int* __restrict__ fac
 
 // ---- render --------------------------------------------------------------------------------------------------------------------
 
-// the 9 entries of R^T, then -R^T t (the header's m and s) of the row-major 3 x 4 pose P
-__device__ inline void camera_rows(const float* __restrict__ P, float* o) {
-    const float t0 = P[3], t1 = P[7], t2 = P[11];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {                       // row r of R^T = column r of R
-        const float a = P[r], b = P[4 + r], cc = P[8 + r];
-        o[3 * r] = a;
-        o[3 * r + 1] = b;
-        o[3 * r + 2] = cc;
-        o[9 + r] = -(a * t0 + b * t1 + cc * t2);
-    }
-}
-
-struct Intrinsics {
-    float k[9];
-};
-
-__device__ inline Intrinsics load_intrinsics(const float* __restrict__ K) {
-    Intrinsics in;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) in.k[i] = K[i];
-    return in;
-}
-
-__device__ inline void project(const float* o, const Intrinsics& in, float x, float y, float z, float& u, float& v, float& d) {
-    const float px = o[0] * x + o[1] * y + o[2] * z + o[9];
-    const float py = o[3] * x + o[4] * y + o[5] * z + o[10];
-    const float pz = o[6] * x + o[7] * y + o[8] * z + o[11];
-    const float ud = in.k[0] * px + in.k[1] * py + in.k[2] * pz, vd = in.k[3] * px + in.k[4] * py + in.k[5] * pz;
-    d = in.k[6] * px + in.k[7] * py + in.k[8] * pz;
-    u = ud / d;
-    v = vd / d;
-}
-
-// a face on one camera's screen: the points A, B, C, 1 / d of each, the signed area, the clipped pixel box and the face's index
-struct Tri {
-    float ax, ay, bx, by, cx, cy, qa, qb, qc, area;
-    int i0, i1, j0, j1;
-    unsigned face;
-};
-
-__device__ inline float edge(float ax, float ay, float bx, float by, float px, float py) { return (bx - ax) * (py - ay) - (by - ay) * (px - ax); }
-
-__device__ inline void project_face(const float* o, const Intrinsics& in, const float x[3][3], Tri& t, float& da, float& db, float& dc) {
-    project(o, in, x[0][0], x[0][1], x[0][2], t.ax, t.ay, da);
-    project(o, in, x[1][0], x[1][1], x[1][2], t.bx, t.by, db);
-    project(o, in, x[2][0], x[2][1], x[2][2], t.cx, t.cy, dc);
-    t.qa = 1.0f / da;
-    t.qb = 1.0f / db;
-    t.qc = 1.0f / dc;
-    t.area = edge(t.ax, t.ay, t.bx, t.by, t.cx, t.cy);
-}
-
-// pixel (i, j), inside [0, W) x [0, H), of the camera whose keys are kb: inside test on the centre, depth, minimum of (depth, face)
-__device__ inline void visit(const Tri& t, int i, int j, unsigned long long* kb, int W) {
-    const float px = (float)i + 0.5f, py = (float)j + 0.5f;
-    const float wa = edge(t.bx, t.by, t.cx, t.cy, px, py), wb = edge(t.cx, t.cy, t.ax, t.ay, px, py), wc = edge(t.ax, t.ay, t.bx, t.by, px, py);
-    const bool covered = t.area > 0.f ? (wa >= 0.f && wb >= 0.f && wc >= 0.f) : (wa <= 0.f && wb <= 0.f && wc <= 0.f);
-    if (!covered) return;
-    const float z = t.area / (wa * t.qa + wb * t.qb + wc * t.qc);
-    if (!(z > 0.f && z < INF)) return;
-    unsigned long long* p = kb + (size_t)j * W + i;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | t.face;
-    if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
-}
+#include "../mesh_camera.h"
+#include "../mesh_raster.h"
 
 __global__ __launch_bounds__(THREADS) void atlas_raster(const float* __restrict__ vertices, const int* __restrict__ faces, long long n_v,
                                                         long long n_f, const float* __restrict__ K, const float* __restrict__ poses,
                                                         long long cam0, int nc, int W, int H, float near_distance,
                                                         unsigned long long* keys) {
-    __shared__ float s_cam[12 * CAM_TILE];
-    for (int i = threadIdx.x; i < nc; i += blockDim.x) camera_rows(poses + 12 * (size_t)(cam0 + i), s_cam + 12 * i);
-    __syncthreads();
-    const long long f = (long long)blockIdx.x * THREADS + threadIdx.x;
-    int idx[3];
-    const bool valid = f < n_f && load_face(faces, f, (unsigned)n_v, idx);
-    float x[3][3] = {};
-    if (valid) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float* p = vertices + 3 * (size_t)idx[k];
-            x[k][0] = p[0];
-            x[k][1] = p[1];
-            x[k][2] = p[2];
-        }
-    }
-    const Intrinsics in = load_intrinsics(K);
-    const int lane = threadIdx.x & 63;
-    const float wmax = (float)(W - 1), hmax = (float)(H - 1);
-    for (int ci = 0; ci < nc; ++ci) {                   // wave-uniform: every lane takes part in the ballots below
-        const float* o = s_cam + 12 * ci;
-        unsigned long long* kb = keys + (size_t)ci * H * W;
-        Tri t;
-        float da, db, dc;
-        project_face(o, in, x, t, da, db, dc);
-        t.face = (unsigned)f;
-        bool ok = valid && da >= near_distance && db >= near_distance && dc >= near_distance;
-        ok = ok && t.area != 0.f && fabsf(t.area) < INF;
-        const float fi0 = fmaxf(0.f, floorf(fminf(fminf(t.ax, t.bx), t.cx))), fi1 = fminf(wmax, floorf(fmaxf(fmaxf(t.ax, t.bx), t.cx)));
-        const float fj0 = fmaxf(0.f, floorf(fminf(fminf(t.ay, t.by), t.cy))), fj1 = fminf(hmax, floorf(fmaxf(fmaxf(t.ay, t.by), t.cy)));
-        ok = ok && fi0 <= fi1 && fj0 <= fj1;            // false when a bound is NaN
-        t.i0 = ok ? (int)fi0 : 0;                       // inside [0, W - 1] x [0, H - 1] when ok
-        t.i1 = ok ? (int)fi1 : -1;
-        t.j0 = ok ? (int)fj0 : 0;
-        t.j1 = ok ? (int)fj1 : -1;
-        const bool big = ok && (long long)(t.i1 - t.i0 + 1) * (t.j1 - t.j0 + 1) > SMALL_BOX;
-        if (ok && !big) {
-            for (int j = t.j0; j <= t.j1; ++j)
-                for (int i = t.i0; i <= t.i1; ++i) visit(t, i, j, kb, W);
-        }
-        unsigned long long todo = __ballot(big);        // the same mask in every lane: the loop below is wave-uniform
-        while (todo) {                                  // the wave walks each large box together
-            const int leader = __ffsll((long long)todo) - 1;
-            Tri w;
-            w.ax = __shfl(t.ax, leader, 64);
-            w.ay = __shfl(t.ay, leader, 64);
-            w.bx = __shfl(t.bx, leader, 64);
-            w.by = __shfl(t.by, leader, 64);
-            w.cx = __shfl(t.cx, leader, 64);
-            w.cy = __shfl(t.cy, leader, 64);
-            w.qa = __shfl(t.qa, leader, 64);
-            w.qb = __shfl(t.qb, leader, 64);
-            w.qc = __shfl(t.qc, leader, 64);
-            w.area = __shfl(t.area, leader, 64);
-            w.i0 = __shfl(t.i0, leader, 64);
-            w.i1 = __shfl(t.i1, leader, 64);
-            w.j0 = __shfl(t.j0, leader, 64);
-            w.j1 = __shfl(t.j1, leader, 64);
-            w.face = (unsigned)__shfl((int)t.face, leader, 64);
-            for (int j = w.j0 + (lane >> 3); j <= w.j1; j += 8)      // no cross-lane operation inside: lanes may run out apart
-                for (int i = w.i0 + (lane & 7); i <= w.i1; i += 8) visit(w, i, j, kb, W);
-            todo &= todo - 1;
-        }
-    }
+    raster_faces(KeySink{}, vertices, faces, n_v, n_f, K, poses, cam0, nc, W, H, near_distance, keys);
 }
 
 // grid: (blocks over H * W, cameras of the launch)
@@ -549,44 +421,14 @@ __global__ __launch_bounds__(THREADS) void atlas_shade(const float* __restrict__
     if (key != NO_KEY && kf < (unsigned long long)n_f && load_face(faces, kf, (unsigned)n_v, idx)) {   // a key only ever names a face the raster accepted
         face = (int)kf;
         z = __uint_as_float((unsigned)(key >> 32));
-        float o[12], x[3][3];
-        camera_rows(poses + 12 * (size_t)(cam0 + ci), o);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float* p = vertices + 3 * (size_t)idx[k];
-            x[k][0] = p[0];
-            x[k][1] = p[1];
-            x[k][2] = p[2];
-        }
-        const Intrinsics in = load_intrinsics(K);
-        Tri t;
-        float da, db, dc;
-        project_face(o, in, x, t, da, db, dc);
-        const int j = pix / W, i = pix - j * W;
-        const float px = (float)i + 0.5f, py = (float)j + 0.5f;
-        const float wa = edge(t.bx, t.by, t.cx, t.cy, px, py), wb = edge(t.cx, t.cy, t.ax, t.ay, px, py), wc = edge(t.ax, t.ay, t.bx, t.by, px, py);
-        const float la = wa * t.qa, lb = wb * t.qb, lc = wc * t.qc;
-        const float sum = (la + lb) + lc;
-        const float beta = fminf(fmaxf(lb / sum, 0.f), 1.f), gamma = fminf(fmaxf(lc / sum, 0.f), 1.f);
+        float beta, gamma;
+        winner_weights(vertices, idx, K, poses + 12 * (size_t)(cam0 + ci), pix, W, beta, gamma);
         const Place pl = load_place(face_place, (size_t)kf);
         const float xs = 1.0f + beta * (float)pl.T, ys = 1.0f + gamma * (float)pl.T;
         const float ox = (float)pl.ox, oy = (float)pl.oy;
         const float X = pl.slot ? ox + ((float)(pl.T + 4) - xs) : ox + xs;
         const float Y = pl.slot ? oy + ((float)(pl.T + 3) - ys) : oy + ys;
-        const float flx = floorf(X), fly = floorf(Y);
-        const float fx = X - flx, fy = Y - fly;
-        // X and Y are finite and below 2^17: the casts are exact, and the clamps keep every read inside the atlas whatever
-        // face_place holds
-        const int i0 = min(max((int)flx, 0), AW - 1), j0 = min(max((int)fly, 0), AH - 1);
-        const int i1 = min(i0 + 1, AW - 1), j1 = min(j0 + 1, AH - 1);
-        const uint8_t *t00 = texture + 3 * ((size_t)j0 * AW + i0), *t10 = texture + 3 * ((size_t)j0 * AW + i1);
-        const uint8_t *t01 = texture + 3 * ((size_t)j1 * AW + i0), *t11 = texture + 3 * ((size_t)j1 * AW + i1);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float top = (float)t00[c] * (1.0f - fx) + (float)t10[c] * fx;
-            const float bot = (float)t01[c] * (1.0f - fx) + (float)t11[c] * fx;
-            rgb[c] = (top * (1.0f - fy) + bot * fy) / 255.0f;
-        }
+        atlas_bilinear(texture, AW, AH, X, Y, rgb);     // whatever face_place holds, every read stays inside the atlas
     }
     image[3 * out_px] = rgb[0];
     image[3 * out_px + 1] = rgb[1];

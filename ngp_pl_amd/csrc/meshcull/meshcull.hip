@@ -4,14 +4,12 @@
 //
 // Views, per chunk of as many cameras as the caller's depth workspace holds, on the caller's stream:
 //   clear            the chunk's buffers to the bits of +inf (hipMemsetD32Async);
-//   cull_raster      one work item per (face, camera): a thread holds its face's three vertices in registers and walks the
-//                    cameras of the launch (at most CAM_TILE, their R^T and -R^T t in LDS), re-projecting the vertices for each.
-//                    A clipped pixel box of at most SMALL_BOX pixels is walked by the face's own lane; larger boxes are collected
-//                    with a ballot and walked by the whole wave, one box after the other, the lanes as an 8 x 8 pixel tile that
-//                    strides the box.  Both walkers run the same per-pixel function and the buffer takes a minimum, so which of
-//                    them visits a pixel changes the time only.  atomicMin on the depth's bits, skipped when an L2 read of the
-//                    pixel already holds a smaller or equal depth (the buffer only ever falls, so a skipped write is never missed);
-//   cull_test        one thread per vertex walks the same cameras and adds the views it has: a plain per-vertex sum, no atomic.
+//   cull_raster      the shared rasteriser of ../mesh_raster.h (one work item per (face, camera), at most CAM_TILE cameras per
+//                    launch, a lane walker for small pixel boxes and a wave walker for large ones) with the sink DepthSink:
+//                    atomicMin on the depth's bits, skipped when an L2 read of the pixel already holds a smaller or equal depth
+//                    (the buffer only ever falls, so a skipped write is never missed);
+//   cull_test        one thread per vertex walks the same cameras (../mesh_camera.h) and adds the views it has: a plain
+//                    per-vertex sum, no atomic.
 // Compaction is the shared one of ../mesh_compact.h with the rule ViewsKeep (a face is kept iff a vertex of it has min_views views).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,143 +20,23 @@
 
 namespace {
 
-#include "../mesh_compact.h"
+#include "../mesh_compact.h"                           // THREADS and load_face, which mesh_raster.h expects
+#include "../mesh_camera.h"
+#include "../mesh_raster.h"
 
-constexpr int CAM_TILE = 128;                           // cameras per launch: 12 floats each in LDS
-constexpr int SMALL_BOX = 64;                           // pixels a lane walks on its own
 constexpr int MAX_WH = 16384;
 constexpr unsigned INF_BITS = 0x7F800000u;
 
 // per camera of the launch: the 9 entries of R^T, then -R^T t (the header's m and s)
 __device__ inline void load_cameras(const float* __restrict__ poses, long long cam0, int nc, float* s_cam) {
-    for (int i = threadIdx.x; i < nc; i += blockDim.x) {
-        const float* P = poses + 12 * (size_t)(cam0 + i);   // row-major 3 x 4: [R | t]
-        float* o = s_cam + 12 * i;
-        const float t0 = P[3], t1 = P[7], t2 = P[11];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {                   // row r of R^T = column r of R
-            const float a = P[r], b = P[4 + r], cc = P[8 + r];
-            o[3 * r] = a;
-            o[3 * r + 1] = b;
-            o[3 * r + 2] = cc;
-            o[9 + r] = -(a * t0 + b * t1 + cc * t2);
-        }
-    }
+    for (int i = threadIdx.x; i < nc; i += blockDim.x) camera_rows(poses + 12 * (size_t)(cam0 + i), s_cam + 12 * i);
     __syncthreads();
-}
-
-struct Intrinsics {
-    float k[9];
-};
-
-__device__ inline Intrinsics load_intrinsics(const float* __restrict__ K) {
-    Intrinsics in;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) in.k[i] = K[i];
-    return in;
-}
-
-__device__ inline void project(const float* o, const Intrinsics& in, float x, float y, float z, float& u, float& v, float& d) {
-    const float px = o[0] * x + o[1] * y + o[2] * z + o[9];
-    const float py = o[3] * x + o[4] * y + o[5] * z + o[10];
-    const float pz = o[6] * x + o[7] * y + o[8] * z + o[11];
-    const float ud = in.k[0] * px + in.k[1] * py + in.k[2] * pz, vd = in.k[3] * px + in.k[4] * py + in.k[5] * pz;
-    d = in.k[6] * px + in.k[7] * py + in.k[8] * pz;
-    u = ud / d;
-    v = vd / d;
-}
-
-// a face on one camera's screen: the points A, B, C, 1 / d of each, the signed area and the clipped pixel box
-struct Tri {
-    float ax, ay, bx, by, cx, cy, qa, qb, qc, area;
-    int i0, i1, j0, j1;
-};
-
-__device__ inline float edge(float ax, float ay, float bx, float by, float px, float py) { return (bx - ax) * (py - ay) - (by - ay) * (px - ax); }
-
-// pixel (i, j) of the camera whose buffer is zb: inside test on the centre, perspective-correct depth, minimum
-__device__ inline void shade(const Tri& t, int i, int j, unsigned* zb, int W) {
-    const float px = (float)i + 0.5f, py = (float)j + 0.5f;
-    const float wa = edge(t.bx, t.by, t.cx, t.cy, px, py), wb = edge(t.cx, t.cy, t.ax, t.ay, px, py), wc = edge(t.ax, t.ay, t.bx, t.by, px, py);
-    const bool covered = t.area > 0.f ? (wa >= 0.f && wb >= 0.f && wc >= 0.f) : (wa <= 0.f && wb <= 0.f && wc <= 0.f);
-    if (!covered) return;
-    const float z = t.area / (wa * t.qa + wb * t.qb + wc * t.qc);
-    if (!(z > 0.f && z < __uint_as_float(INF_BITS))) return;
-    unsigned* p = zb + (size_t)j * W + i;
-    const unsigned bits = __float_as_uint(z);
-    if (bits < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, bits);
 }
 
 __global__ __launch_bounds__(THREADS) void cull_raster(const float* __restrict__ vertices, const int* __restrict__ faces, long long n_v,
                                                        long long n_f, const float* __restrict__ K, const float* __restrict__ poses,
                                                        long long cam0, int nc, int W, int H, float near_distance, unsigned* zbuf) {
-    __shared__ float s_cam[12 * CAM_TILE];
-    load_cameras(poses, cam0, nc, s_cam);
-    const long long f = (long long)blockIdx.x * THREADS + threadIdx.x;
-    int idx[3];
-    const bool valid = f < n_f && load_face(faces, f, (unsigned)n_v, idx);
-    float x[3][3] = {};
-    if (valid) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float* p = vertices + 3 * (size_t)idx[k];
-            x[k][0] = p[0];
-            x[k][1] = p[1];
-            x[k][2] = p[2];
-        }
-    }
-    const Intrinsics in = load_intrinsics(K);
-    const int lane = threadIdx.x & 63;
-    const float wmax = (float)(W - 1), hmax = (float)(H - 1);
-    for (int ci = 0; ci < nc; ++ci) {                   // wave-uniform: every lane takes part in the ballots below
-        const float* o = s_cam + 12 * ci;
-        unsigned* zb = zbuf + (size_t)ci * H * W;
-        Tri t;
-        float da, db, dc;
-        project(o, in, x[0][0], x[0][1], x[0][2], t.ax, t.ay, da);
-        project(o, in, x[1][0], x[1][1], x[1][2], t.bx, t.by, db);
-        project(o, in, x[2][0], x[2][1], x[2][2], t.cx, t.cy, dc);
-        t.qa = 1.0f / da;
-        t.qb = 1.0f / db;
-        t.qc = 1.0f / dc;
-        t.area = edge(t.ax, t.ay, t.bx, t.by, t.cx, t.cy);
-        bool ok = valid && da >= near_distance && db >= near_distance && dc >= near_distance;
-        ok = ok && t.area != 0.f && fabsf(t.area) < __uint_as_float(INF_BITS);
-        const float fi0 = fmaxf(0.f, floorf(fminf(fminf(t.ax, t.bx), t.cx))), fi1 = fminf(wmax, floorf(fmaxf(fmaxf(t.ax, t.bx), t.cx)));
-        const float fj0 = fmaxf(0.f, floorf(fminf(fminf(t.ay, t.by), t.cy))), fj1 = fminf(hmax, floorf(fmaxf(fmaxf(t.ay, t.by), t.cy)));
-        ok = ok && fi0 <= fi1 && fj0 <= fj1;
-        t.i0 = ok ? (int)fi0 : 0;                       // inside [0, W - 1] x [0, H - 1] when ok
-        t.i1 = ok ? (int)fi1 : -1;
-        t.j0 = ok ? (int)fj0 : 0;
-        t.j1 = ok ? (int)fj1 : -1;
-        const bool big = ok && (t.i1 - t.i0 + 1) * (t.j1 - t.j0 + 1) > SMALL_BOX;
-        if (ok && !big) {
-            for (int j = t.j0; j <= t.j1; ++j)
-                for (int i = t.i0; i <= t.i1; ++i) shade(t, i, j, zb, W);
-        }
-        unsigned long long todo = __ballot(big);
-        while (todo) {                                  // the wave walks each large box together
-            const int leader = __ffsll((long long)todo) - 1;
-            Tri w;
-            w.ax = __shfl(t.ax, leader, 64);
-            w.ay = __shfl(t.ay, leader, 64);
-            w.bx = __shfl(t.bx, leader, 64);
-            w.by = __shfl(t.by, leader, 64);
-            w.cx = __shfl(t.cx, leader, 64);
-            w.cy = __shfl(t.cy, leader, 64);
-            w.qa = __shfl(t.qa, leader, 64);
-            w.qb = __shfl(t.qb, leader, 64);
-            w.qc = __shfl(t.qc, leader, 64);
-            w.area = __shfl(t.area, leader, 64);
-            w.i0 = __shfl(t.i0, leader, 64);
-            w.i1 = __shfl(t.i1, leader, 64);
-            w.j0 = __shfl(t.j0, leader, 64);
-            w.j1 = __shfl(t.j1, leader, 64);
-            for (int j = w.j0 + (lane >> 3); j <= w.j1; j += 8)
-                for (int i = w.i0 + (lane & 7); i <= w.i1; i += 8) shade(w, i, j, zb, W);
-            todo &= todo - 1;
-        }
-    }
+    raster_faces(DepthSink{}, vertices, faces, n_v, n_f, K, poses, cam0, nc, W, H, near_distance, zbuf);
 }
 
 __global__ __launch_bounds__(THREADS) void cull_test(const float* __restrict__ vertices, long long n_v, const float* __restrict__ K,

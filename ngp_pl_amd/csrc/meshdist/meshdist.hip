@@ -10,7 +10,8 @@
 //                   the slot in pass 2.
 //   query           one query per lane.  Samples come in face order and marching cubes emits faces in lattice order, so the 64 lanes
 //                   of a wave walk neighbouring cells and mostly the same lists: the list and vertex loads of a wave hit the same
-//                   lines.  The best key lives in one 64-bit register pair; there is no per-thread array.
+//                   lines.  The walk, the closest point and the grid's cells are ../mesh_nearest.h, shared with
+//                   libngp_meshnormal.so; here every candidate is accepted.
 //   stats / stats_finish   the two-stage f64 sums of rule 4, as libngp_metrics.so does them.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -29,26 +30,11 @@ constexpr int NT = NGP_MESHDIST_MAX_THRESHOLDS;
 constexpr int NOUT = NGP_MESHDIST_STATS_OUTPUTS;
 constexpr int STATS_MAX_BLOCKS = NGP_MESHDIST_STATS_MAX_BLOCKS;
 constexpr float SLACK_FACTOR = (float)NGP_MESHDIST_SLACK_ULPS * 0x1p-23f;
+constexpr int MAX_AXIS = NGP_MESHDIST_MAX_AXIS;
+constexpr long long MAX_CELLS = NGP_MESHDIST_MAX_CELLS;
 static_assert(NGP_MESHDIST_SCAN_BLOCK % THREADS == 0 && NOUT == 6 + NT, "header constants");
 
-struct V3 {
-    float x, y, z;
-};
-__device__ inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ inline V3 load3(const float* __restrict__ p, long long i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-__device__ inline bool finite3(V3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
-__device__ inline float absmax3(V3 a) { return fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fabsf(a.z)); }
-
-// the three vertices of a usable face; false otherwise
-__device__ inline bool load_face(const float* __restrict__ v, const int32_t* __restrict__ f, int n_v, long long face, V3& a, V3& b, V3& c) {
-    const int ia = f[3 * face], ib = f[3 * face + 1], ic = f[3 * face + 2];
-    if ((unsigned)ia >= (unsigned)n_v || (unsigned)ib >= (unsigned)n_v || (unsigned)ic >= (unsigned)n_v) return false;
-    a = load3(v, ia);
-    b = load3(v, ib);
-    c = load3(v, ic);
-    return finite3(a) && finite3(b) && finite3(c);
-}
+#include "../mesh_nearest.h"
 
 // rule 1: k
 __device__ inline int subdivision(V3 a, V3 b, V3 c, float spacing) {
@@ -65,57 +51,6 @@ __device__ inline int isqrt_small(int s) {                  // s < 2^22
     while (r * r > s) --r;
     while ((r + 1) * (r + 1) <= s) ++r;
     return r;
-}
-
-// rule 2: the closest point of (a, b, c) to p
-__device__ inline V3 closest_point(V3 p, V3 a, V3 b, V3 c) {
-    const V3 ab = sub(b, a), ac = sub(c, a), ap = sub(p, a);
-    const float d1 = dot(ab, ap), d2 = dot(ac, ap);
-    if (d1 <= 0.0f && d2 <= 0.0f) return a;
-    const V3 bp = sub(p, b);
-    const float d3 = dot(ab, bp), d4 = dot(ac, bp);
-    if (d3 >= 0.0f && d4 <= d3) return b;
-    const float vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
-        const float v = d1 / (d1 - d3);
-        return {a.x + v * ab.x, a.y + v * ab.y, a.z + v * ab.z};
-    }
-    const V3 cp = sub(p, c);
-    const float d5 = dot(ab, cp), d6 = dot(ac, cp);
-    if (d6 >= 0.0f && d5 <= d6) return c;
-    const float vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
-        const float w = d2 / (d2 - d6);
-        return {a.x + w * ac.x, a.y + w * ac.y, a.z + w * ac.z};
-    }
-    const float va = d3 * d6 - d5 * d4;
-    const float s43 = d4 - d3, s56 = d5 - d6;
-    if (va <= 0.0f && s43 >= 0.0f && s56 >= 0.0f) {
-        const float w = s43 / (s43 + s56);
-        const V3 bc = sub(c, b);
-        return {b.x + w * bc.x, b.y + w * bc.y, b.z + w * bc.z};
-    }
-    const float denom = 1.0f / ((va + vb) + vc);
-    float v = vb * denom, w = vc * denom;
-    if (!(v >= 0.0f)) v = 0.0f;
-    if (v > 1.0f) v = 1.0f;
-    if (!(w >= 0.0f)) w = 0.0f;
-    const float rest = 1.0f - v;
-    if (w > rest) w = rest;
-    return {(a.x + v * ab.x) + w * ac.x, (a.y + v * ab.y) + w * ac.y, (a.z + v * ab.z) + w * ac.z};
-}
-
-__device__ inline float squared_distance(V3 p, V3 q) {
-    const V3 e = sub(p, q);
-    return (e.x * e.x + e.y * e.y) + e.z * e.z;
-}
-
-// THE GRID: the clamped cell of a coordinate
-__device__ inline int cell_of(float t, float o, float cell, int n) {
-    const float g = floorf((t - o) / cell);
-    if (!(g >= 0.0f)) return 0;
-    if (g >= (float)n) return n - 1;
-    return (int)g;
 }
 
 // ---- the sampler
@@ -238,11 +173,6 @@ __global__ __launch_bounds__(THREADS) void emit_samples(const float* __restrict_
 
 // ---- the grid
 
-struct Grid {
-    float ox, oy, oz, cell, m_grid;
-    int nx, ny, nz;
-};
-
 // pass 1 (FILL = false): counts[cell] += 1; pass 2: entries[start[cell] + cursor[cell]++] = face
 template <bool FILL>
 __global__ __launch_bounds__(THREADS) void bin_faces(const float* __restrict__ v, const int32_t* __restrict__ f, int n_v, int n_f, Grid g,
@@ -280,44 +210,7 @@ __global__ __launch_bounds__(THREADS) void query(const float* __restrict__ point
     const V3 p = load3(points, i);
     unsigned long long best = ~0ull;                        // bits(d2) << 32 | face
     uint32_t shells = 0, evaluated = 0;
-    if (finite3(p)) {
-        const float sq = SLACK_FACTOR * fmaxf(g.m_grid, absmax3(p));
-        const int cx = cell_of(p.x, g.ox, g.cell, g.nx), cy = cell_of(p.y, g.oy, g.cell, g.ny), cz = cell_of(p.z, g.oz, g.cell, g.nz);
-        for (int r = 0;; ++r) {
-            ++shells;
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
-            for (int z = z0; z <= z1; ++z) {
-                const bool zface = z == cz - r || z == cz + r;
-                for (int y = y0; y <= y1; ++y) {
-                    // a row of the shell: all of [cx - r, cx + r] on a z or y face of the cube, else its two ends
-                    const bool full = zface || y == cy - r || y == cy + r;
-                    const int step = full || r == 0 ? 1 : 2 * r;
-                    for (int x = cx - r; x <= cx + r; x += step) {
-                        if (x < 0 || x >= g.nx) continue;
-                        const long long cell = ((long long)z * g.ny + y) * g.nx + x;
-                        const uint32_t e0 = start[cell], e1 = min(start[cell + 1], (uint32_t)n_entries);
-                        for (uint32_t e = e0; e < e1; ++e) {
-                            const int face = entries[e];
-                            if ((unsigned)face >= (unsigned)n_f) continue;
-                            V3 a, b, c;
-                            if (!load_face(v, f, n_v, face, a, b, c)) continue;
-                            const float d2 = squared_distance(p, closest_point(p, a, b, c));
-                            ++evaluated;
-                            if (!(d2 <= 3.402823466e38f)) continue;             // not finite: contributes nothing
-                            const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)face;
-                            best = key < best ? key : best;
-                        }
-                    }
-                }
-            }
-            const float rc = (float)r * g.cell;
-            const float best_d2 = __uint_as_float((uint32_t)(best >> 32));      // NaN bits while nothing was found: the test is false
-            if (sqrtf(best_d2) + sq <= rc) break;
-            if (rc - sq > max_dist) break;
-            const int q = r + 1;                            // the next shell lies wholly outside the grid
-            if (cx - q < 0 && cx + q >= g.nx && cy - q < 0 && cy + q >= g.ny && cz - q < 0 && cz + q >= g.nz) break;
-        }
-    }
+    if (finite3(p)) best = nearest_face(p, AcceptAll{}, v, f, n_v, n_f, g, SLACK_FACTOR, max_dist, start, entries, n_entries, &shells, &evaluated);
     float d2 = __uint_as_float((uint32_t)(best >> 32));
     int face = (int)(uint32_t)best;
     const float nan = __uint_as_float(0x7FC00000u);
@@ -471,31 +364,12 @@ inline GridWs grid_ws(const void* ws, long long cells) {
     return w;
 }
 
-inline bool axes_ok(int nx, int ny, int nz) {
-    const int m = NGP_MESHDIST_MAX_AXIS;
-    return nx >= 1 && ny >= 1 && nz >= 1 && nx <= m && ny <= m && nz <= m && (long long)nx * ny * nz <= NGP_MESHDIST_MAX_CELLS;
-}
-
-// M_grid of the header, or a negative value for a grid that is refused
-inline float grid_magnitude(const float* origin, float cell, int nx, int ny, int nz) {
-    if (!origin || !axes_ok(nx, ny, nz) || !(cell > 0.0f) || !isfinite(cell)) return -1.0f;
-    const int n[3] = {nx, ny, nz};
-    float m = 0.0f;
-    for (int k = 0; k < 3; ++k) {
-        if (!isfinite(origin[k])) return -1.0f;
-        const float far = origin[k] + (float)n[k] * cell;
-        if (!isfinite(far)) return -1.0f;
-        m = fmaxf(m, fmaxf(fabsf(origin[k]), fabsf(far)));
-    }
-    return m;
-}
-
 // the shared checks of the three grid entry points: 0, NGP_EINVAL or NGP_ERANGE; fills g
 inline int check_grid(const void* vertices, const void* faces, int64_t n_vertices, int64_t n_faces, const float* origin, float cell, int nx,
                       int ny, int nz, const void* workspace, size_t workspace_bytes, Grid& g) {
     if (n_vertices < 0 || n_faces < 0 || !origin || !workspace) return NGP_EINVAL;
     if ((!vertices && n_vertices > 0) || (!faces && n_faces > 0)) return NGP_EINVAL;
-    const float m = grid_magnitude(origin, cell, nx, ny, nz);
+    const float m = grid_magnitude(origin, cell, nx, ny, nz, MAX_AXIS, MAX_CELLS);
     if (m < 0.0f) return NGP_EINVAL;
     if (cell < (float)NGP_MESHDIST_MIN_CELL_SLACKS * (SLACK_FACTOR * m)) return NGP_EINVAL;
     if (n_vertices > INT32_MAX || n_faces > INT32_MAX) return NGP_ERANGE;
@@ -521,7 +395,7 @@ NGP_API const char* ngp_meshdist_build_arch(void) { return "gfx950"; }
 
 NGP_API int ngp_meshdist_slack(const float* origin, float cell, int nx, int ny, int nz, float* slack, float* min_cell) {
     if (!slack || !min_cell) return NGP_EINVAL;
-    const float m = grid_magnitude(origin, cell, nx, ny, nz);
+    const float m = grid_magnitude(origin, cell, nx, ny, nz, MAX_AXIS, MAX_CELLS);
     if (m < 0.0f) return NGP_EINVAL;
     *slack = SLACK_FACTOR * m;
     *min_cell = (float)NGP_MESHDIST_MIN_CELL_SLACKS * (SLACK_FACTOR * m);
@@ -566,7 +440,7 @@ NGP_API int ngp_meshdist_sample_emit(const float* vertices, const int32_t* faces
 }
 
 NGP_API size_t ngp_meshdist_grid_workspace_bytes(int nx, int ny, int nz) {
-    if (!axes_ok(nx, ny, nz)) return 0;
+    if (!axes_ok(nx, ny, nz, MAX_AXIS, MAX_CELLS)) return 0;
     const long long cells = (long long)nx * ny * nz;
     return 8 * (size_t)scan_blocks(cells) + 4 * (size_t)(cells + 1) + 4 * (size_t)cells;
 }

@@ -5,9 +5,9 @@
 //
 //   transfer   one query per lane, workgroups of 256.  Texels come in row-major atlas order, so the 64 lanes of a wave are
 //              neighbours on one or two faces of the simplified mesh and walk the same cell lists of the detail mesh's grid: the
-//              list, index and vertex loads of a wave hit the same lines.  The best key lives in one 64-bit register pair; the
-//              barycentric pair is recomputed for the winner once the walk is over, so nothing per candidate is kept and there is
-//              no per-thread array.  An invalid texel leaves before it loads anything else.
+//              list, index and vertex loads of a wave hit the same lines.  The walk is nearest_face of ../mesh_nearest.h, the one
+//              libngp_meshdist.so's query runs, with the filter Oriented; the barycentric pair is recomputed for the winner once
+//              the walk is over, so nothing per candidate is kept.  An invalid texel leaves before it loads anything else.
 //   shade      one pixel per lane.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -23,24 +23,7 @@ constexpr int THREADS = 256;
 constexpr float SLACK_FACTOR = (float)NGP_MESHNORMAL_SLACK_ULPS * 0x1p-23f;
 constexpr int MAX_WH = 16384;
 
-struct V3 {
-    float x, y, z;
-};
-__device__ inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ inline V3 load3(const float* __restrict__ p, long long i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-__device__ inline bool finite3(V3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
-__device__ inline float absmax3(V3 a) { return fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fabsf(a.z)); }
-
-// the three vertices of a usable face; false otherwise
-__device__ inline bool load_face(const float* __restrict__ v, const int32_t* __restrict__ f, int n_v, long long face, V3& a, V3& b, V3& c) {
-    const int ia = f[3 * face], ib = f[3 * face + 1], ic = f[3 * face + 2];
-    if ((unsigned)ia >= (unsigned)n_v || (unsigned)ib >= (unsigned)n_v || (unsigned)ic >= (unsigned)n_v) return false;
-    a = load3(v, ia);
-    b = load3(v, ib);
-    c = load3(v, ic);
-    return finite3(a) && finite3(b) && finite3(c);
-}
+#include "../mesh_nearest.h"
 
 // rule 1: the face faces the way m does
 __device__ inline bool faces_along(V3 a, V3 b, V3 c, V3 m) {
@@ -49,71 +32,11 @@ __device__ inline bool faces_along(V3 a, V3 b, V3 c, V3 m) {
     return dot(g, m) > 0.0f;
 }
 
-// rule 2: the closest point of (a, b, c) to p and the barycentric pair of the deciding case
-__device__ inline V3 closest_point(V3 p, V3 a, V3 b, V3 c, float& bv, float& bw) {
-    const V3 ab = sub(b, a), ac = sub(c, a), ap = sub(p, a);
-    const float d1 = dot(ab, ap), d2 = dot(ac, ap);
-    bv = 0.0f, bw = 0.0f;
-    if (d1 <= 0.0f && d2 <= 0.0f) return a;
-    const V3 bp = sub(p, b);
-    const float d3 = dot(ab, bp), d4 = dot(ac, bp);
-    if (d3 >= 0.0f && d4 <= d3) {
-        bv = 1.0f;
-        return b;
-    }
-    const float vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
-        const float v = d1 / (d1 - d3);
-        bv = v;
-        return {a.x + v * ab.x, a.y + v * ab.y, a.z + v * ab.z};
-    }
-    const V3 cp = sub(p, c);
-    const float d5 = dot(ab, cp), d6 = dot(ac, cp);
-    if (d6 >= 0.0f && d5 <= d6) {
-        bw = 1.0f;
-        return c;
-    }
-    const float vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
-        const float w = d2 / (d2 - d6);
-        bw = w;
-        return {a.x + w * ac.x, a.y + w * ac.y, a.z + w * ac.z};
-    }
-    const float va = d3 * d6 - d5 * d4;
-    const float s43 = d4 - d3, s56 = d5 - d6;
-    if (va <= 0.0f && s43 >= 0.0f && s56 >= 0.0f) {
-        const float w = s43 / (s43 + s56);
-        const V3 bc = sub(c, b);
-        bv = 1.0f - w, bw = w;
-        return {b.x + w * bc.x, b.y + w * bc.y, b.z + w * bc.z};
-    }
-    const float denom = 1.0f / ((va + vb) + vc);
-    float v = vb * denom, w = vc * denom;
-    if (!(v >= 0.0f)) v = 0.0f;
-    if (v > 1.0f) v = 1.0f;
-    if (!(w >= 0.0f)) w = 0.0f;
-    const float rest = 1.0f - v;
-    if (w > rest) w = rest;
-    bv = v, bw = w;
-    return {(a.x + v * ab.x) + w * ac.x, (a.y + v * ab.y) + w * ac.y, (a.z + v * ab.z) + w * ac.z};
-}
-
-__device__ inline float squared_distance(V3 p, V3 q) {
-    const V3 e = sub(p, q);
-    return (e.x * e.x + e.y * e.y) + e.z * e.z;
-}
-
-// THE GRID: the clamped cell of a coordinate
-__device__ inline int cell_of(float t, float o, float cell, int n) {
-    const float g = floorf((t - o) / cell);
-    if (!(g >= 0.0f)) return 0;
-    if (g >= (float)n) return n - 1;
-    return (int)g;
-}
-
-struct Grid {
-    float ox, oy, oz, cell, m_grid;
-    int nx, ny, nz;
+// the walk's filter: under `oriented` only the faces that face the way the query's normal m does
+struct Oriented {
+    V3 m;
+    int oriented;
+    __device__ bool operator()(V3 a, V3 b, V3 c) const { return !oriented || faces_along(a, b, c, m); }
 };
 
 __global__ __launch_bounds__(THREADS) void transfer(const float* __restrict__ points, const float* __restrict__ qnormals,
@@ -138,46 +61,9 @@ __global__ __launch_bounds__(THREADS) void transfer(const float* __restrict__ po
         return;
     }
     const V3 m = load3(qnormals, i);
-    unsigned long long best = ~0ull;                        // bits(d2) << 32 | face
-    int shells = 0, evaluated = 0;
-    const float sq = SLACK_FACTOR * fmaxf(g.m_grid, absmax3(p));
-    const int cx = cell_of(p.x, g.ox, g.cell, g.nx), cy = cell_of(p.y, g.oy, g.cell, g.ny), cz = cell_of(p.z, g.oz, g.cell, g.nz);
-    for (int r = 0;; ++r) {
-        ++shells;
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
-        for (int z = z0; z <= z1; ++z) {
-            const bool zface = z == cz - r || z == cz + r;
-            for (int y = y0; y <= y1; ++y) {
-                // a row of the shell: all of [cx - r, cx + r] on a z or y face of the cube, else its two ends
-                const bool full = zface || y == cy - r || y == cy + r;
-                const int step = full || r == 0 ? 1 : 2 * r;
-                for (int x = cx - r; x <= cx + r; x += step) {
-                    if (x < 0 || x >= g.nx) continue;
-                    const long long cell = ((long long)z * g.ny + y) * g.nx + x;
-                    const uint32_t e0 = start[cell], e1 = min(start[cell + 1], (uint32_t)n_entries);
-                    for (uint32_t e = e0; e < e1; ++e) {
-                        const int face = entries[e];
-                        if ((unsigned)face >= (unsigned)n_f) continue;
-                        V3 a, b, c;
-                        if (!load_face(v, f, n_v, face, a, b, c)) continue;
-                        if (oriented && !faces_along(a, b, c, m)) continue;
-                        float bv, bw;
-                        const float d2 = squared_distance(p, closest_point(p, a, b, c, bv, bw));
-                        ++evaluated;
-                        if (!(d2 <= 3.402823466e38f)) continue;                 // not finite: contributes nothing
-                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)face;
-                        best = key < best ? key : best;
-                    }
-                }
-            }
-        }
-        const float rc = (float)r * g.cell;
-        const float best_d2 = __uint_as_float((uint32_t)(best >> 32));          // NaN bits while nothing was found: the test is false
-        if (sqrtf(best_d2) + sq <= rc) break;
-        if (rc - sq > max_dist) break;
-        const int q = r + 1;                                // the next shell lies wholly outside the grid
-        if (cx - q < 0 && cx + q >= g.nx && cy - q < 0 && cy + q >= g.ny && cz - q < 0 && cz + q >= g.nz) break;
-    }
+    uint32_t shells = 0, evaluated = 0;
+    const unsigned long long best =                         // bits(d2) << 32 | face
+        nearest_face(p, Oriented{m, oriented}, v, f, n_v, n_f, g, SLACK_FACTOR, max_dist, start, entries, n_entries, &shells, &evaluated);
     float d2 = __uint_as_float((uint32_t)(best >> 32));
     int face = (int)(uint32_t)best;
     float bv = 0.0f, bw = 0.0f;
@@ -208,7 +94,7 @@ __global__ __launch_bounds__(THREADS) void transfer(const float* __restrict__ po
     out_d2[i] = d2;
     out_face[i] = face;
     if (bary) bary[2 * i] = bv, bary[2 * i + 1] = bw;
-    if (debug) debug[2 * i] = shells, debug[2 * i + 1] = evaluated;
+    if (debug) debug[2 * i] = (int32_t)shells, debug[2 * i + 1] = (int32_t)evaluated;
 }
 
 __global__ __launch_bounds__(THREADS) void shade(const float* __restrict__ albedo, const float* __restrict__ samples,
@@ -240,25 +126,6 @@ inline int launched() { return (int)hipGetLastError(); }
 
 inline long long scan_blocks(long long n) { return (n + NGP_MESHNORMAL_SCAN_BLOCK - 1) / NGP_MESHNORMAL_SCAN_BLOCK; }
 
-inline bool axes_ok(int nx, int ny, int nz) {
-    const int m = NGP_MESHNORMAL_MAX_AXIS;
-    return nx >= 1 && ny >= 1 && nz >= 1 && nx <= m && ny <= m && nz <= m && (long long)nx * ny * nz <= NGP_MESHNORMAL_MAX_CELLS;
-}
-
-// M_grid of the header, or a negative value for a grid that is refused
-inline float grid_magnitude(const float* origin, float cell, int nx, int ny, int nz) {
-    if (!origin || !axes_ok(nx, ny, nz) || !(cell > 0.0f) || !isfinite(cell)) return -1.0f;
-    const int n[3] = {nx, ny, nz};
-    float m = 0.0f;
-    for (int k = 0; k < 3; ++k) {
-        if (!isfinite(origin[k])) return -1.0f;
-        const float far = origin[k] + (float)n[k] * cell;
-        if (!isfinite(far)) return -1.0f;
-        m = fmaxf(m, fmaxf(fabsf(origin[k]), fabsf(far)));
-    }
-    return m;
-}
-
 }  // namespace
 
 NGP_API int ngp_meshnormal_abi_version(void) { return 1; }
@@ -274,7 +141,7 @@ NGP_API int ngp_meshnormal_transfer(const float* points, const float* query_norm
     if ((!vertices && n_vertices > 0) || (!vertex_normals && n_vertices > 0) || (!faces && n_faces > 0)) return NGP_EINVAL;
     if (n_entries > 0 && !entries) return NGP_EINVAL;
     if (n > 0 && (!points || !query_normals || !valid || !normals_out || !d2 || !face)) return NGP_EINVAL;
-    const float m = grid_magnitude(origin, cell, nx, ny, nz);
+    const float m = grid_magnitude(origin, cell, nx, ny, nz, NGP_MESHNORMAL_MAX_AXIS, NGP_MESHNORMAL_MAX_CELLS);
     if (m < 0.0f) return NGP_EINVAL;
     if (cell < (float)NGP_MESHNORMAL_MIN_CELL_SLACKS * (SLACK_FACTOR * m)) return NGP_EINVAL;
     if (!(max_dist >= 0.0f) || !isfinite(max_dist) || max_dist > (float)NGP_MESHNORMAL_MAX_SHELLS * cell) return NGP_EINVAL;   // THE CAP

@@ -5,7 +5,8 @@
 //   photo_accumulate one thread per point; the 64 points of a wave are consecutive texels of an atlas row, which lie side by side
 //                    on a face, project to neighbouring pixels and so gather their depths and their colours from the same few
 //                    cache lines.  The thread holds its point, its direction and its sums (acc[4], views) in registers and walks
-//                    ALL the cameras of the call in ascending order, tile by tile of CAM_TILE cameras whose R^T, -R^T t and t
+//                    ALL the cameras of the call in ascending order, tile by tile of CAM_TILE cameras whose R^T, -R^T t (camera_rows
+//                    of ../mesh_camera.h, shared with the other camera stages; the projection body is this kernel's own) and t
 //                    pass through LDS (every lane reads the same address: a broadcast): the sums are read once and written once
 //                    per call, and a sequential per-thread sum needs no atomic.  Per camera the cheap rejects (depth, frame,
 //                    viewing angle: tests 1 to 3, registers only) come first; a wave whose ballot shows no lane left skips the
@@ -27,9 +28,7 @@ constexpr int CAM_FLOATS = 16;                          // m (9), s (3), o (3), 
 constexpr int MAX_WH = 16384;
 constexpr unsigned INF_BITS = 0x7F800000u;
 
-struct Intrinsics {
-    float k[9];
-};
+#include "../mesh_camera.h"
 
 struct Params {
     int W, H, guard, power;
@@ -43,18 +42,10 @@ __device__ inline void load_cameras(const float* __restrict__ poses, long long c
     for (int i = threadIdx.x; i < nc; i += blockDim.x) {
         const float* P = poses + 12 * (size_t)(cam0 + i);   // row-major 3 x 4: [R | t]
         float* o = s_cam + CAM_FLOATS * i;
-        const float t0 = P[3], t1 = P[7], t2 = P[11];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {                   // row r of R^T = column r of R
-            const float a = P[r], b = P[4 + r], cc = P[8 + r];
-            o[3 * r] = a;
-            o[3 * r + 1] = b;
-            o[3 * r + 2] = cc;
-            o[9 + r] = -(a * t0 + b * t1 + cc * t2);
-        }
-        o[12] = t0;
-        o[13] = t1;
-        o[14] = t2;
+        camera_rows(P, o);
+        o[12] = P[3];
+        o[13] = P[7];
+        o[14] = P[11];
         o[15] = 0.f;
     }
 }
@@ -101,9 +92,7 @@ __global__ __launch_bounds__(THREADS) void photo_accumulate(const float* __restr
         a3 = a.w;
         views = views_io[p];
     }
-    Intrinsics in;                                      // the same for every thread: scalar loads
-#pragma unroll
-    for (int q = 0; q < 9; ++q) in.k[q] = K[q];
+    const Intrinsics in = load_intrinsics(K);
     const int W = pr.W, H = pr.H;
     const float u_max = (float)W - 0.5f, v_max = (float)H - 0.5f;
     const size_t pixels = (size_t)W * H;

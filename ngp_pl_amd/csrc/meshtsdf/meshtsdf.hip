@@ -5,7 +5,8 @@
 //   tsdf_integrate   one thread per lattice point, x fastest: the 64 points of a wave are a piece of a lattice row (or of two) and
 //                    project to a short pixel segment, so a wave's depth gather touches few lines.  The thread holds its point and
 //                    its state (acc, seen, behind) in registers and walks ALL the cameras of the call in ascending order, tile by
-//                    tile of CAM_TILE cameras whose R^T and -R^T t pass through LDS: the state is read once and written once per
+//                    tile of CAM_TILE cameras whose R^T and -R^T t (camera_rows of ../mesh_camera.h, shared with the other camera
+//                    stages; the projection body is this kernel's own) pass through LDS: the state is read once and written once per
 //                    call, and a sequential per-thread sum needs no atomic.
 //   tsdf_finish      one thread per point: the volume from the state (vol may be acc).
 #include <hip/hip_runtime.h>
@@ -32,25 +33,11 @@ struct Geom {
     float lo[3], h[3];
 };
 
-struct Intrinsics {
-    float k[9];
-};
+#include "../mesh_camera.h"
 
-// per camera of the tile: the 9 entries of R^T, then -R^T t (the header's m and s)
+// per camera of the tile: the 9 entries of R^T, then -R^T t (the header's m and s); the barriers are the caller's
 __device__ inline void load_cameras(const float* __restrict__ poses, long long cam0, int nc, float* s_cam) {
-    for (int i = threadIdx.x; i < nc; i += blockDim.x) {
-        const float* P = poses + 12 * (size_t)(cam0 + i);   // row-major 3 x 4: [R | t]
-        float* o = s_cam + 12 * i;
-        const float t0 = P[3], t1 = P[7], t2 = P[11];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {                   // row r of R^T = column r of R
-            const float a = P[r], b = P[4 + r], cc = P[8 + r];
-            o[3 * r] = a;
-            o[3 * r + 1] = b;
-            o[3 * r + 2] = cc;
-            o[9 + r] = -(a * t0 + b * t1 + cc * t2);
-        }
-    }
+    for (int i = threadIdx.x; i < nc; i += blockDim.x) camera_rows(poses + 12 * (size_t)(cam0 + i), s_cam + 12 * i);
 }
 
 __global__ __launch_bounds__(THREADS) void tsdf_integrate(Dims dm, Geom g, const float* __restrict__ K, const float* __restrict__ poses,
@@ -74,9 +61,7 @@ __global__ __launch_bounds__(THREADS) void tsdf_integrate(Dims dm, Geom g, const
         seen = seen_io[p];
         behind = behind_io[p];
     }
-    Intrinsics in;                                      // the same for every thread: scalar loads
-#pragma unroll
-    for (int q = 0; q < 9; ++q) in.k[q] = K[q];
+    const Intrinsics in = load_intrinsics(K);
     const float wf = (float)W, hf = (float)H, minus_trunc = -trunc;
     const size_t pixels = (size_t)W * H;
     for (long long c0 = 0; c0 < n_cams; c0 += CAM_TILE) {

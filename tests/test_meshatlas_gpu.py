@@ -337,6 +337,65 @@ def test_render_ties_culled_and_empty():
     assert (ids4 == -1).all()
 
 
+def test_cull_tex_and_atlas_depths_agree_bit_for_bit():
+    """The three users of the shared rasteriser see one surface: the cull's depth buffer is the depth of the uniform atlas's render and
+    of the adaptive atlas's, word for word, and the two renders name the same faces.  A 4 x 4 lattice of small quads (lane walker)
+    in front of one face that covers the whole image (wave walker), a medium face between them, a face nearer than near_distance
+    and a face of zero area; three cameras of 37 x 29, the renders two cameras to a chunk."""
+    from ngp_pl_amd import mesh
+    W, H, near, focal = 37, 29, 0.5, 32.0
+    K = F([[focal, 0, 18.5], [0, focal, 14.5], [0, 0, 1]])
+    at = lambda u, v, z: [(u - 18.5) / focal * z, (v - 14.5) / focal * z, z]            # lands on pixel (u, v) of the first camera
+    turn = F([[np.cos(0.05), 0, np.sin(0.05), -0.04], [0, 1, 0, 0.03], [-np.sin(0.05), 0, np.cos(0.05), 0.02]])
+    poses = np.stack([POSE0, F([[1, 0, 0, 0.06], [0, 1, 0, -0.05], [0, 0, 1, -0.03]]), turn])
+    v, f = [], []
+    for j in range(5):
+        for i in range(5):
+            v.append(at(6.3 + 6.1 * i, 3.2 + 5.7 * j, 1.0 + 0.01 * i - 0.02 * j))
+    for j in range(4):
+        for i in range(4):
+            a = 5 * j + i
+            f += [[a, a + 1, a + 6], [a, a + 6, a + 5]]
+    small = len(f)
+    whole = [at(-80, -40, 2.0), at(150, -40, 2.0), at(18, 160, 2.0)]                    # covers every pixel of every camera
+    medium = [at(2, 2, 0.8), at(30, 4, 0.8), at(12, 26, 0.8)]                           # in front of a part of the lattice
+    nearer = [at(10, 10, 0.3), at(30, 10, 0.3), at(20, 25, 0.3)]                        # closer than near_distance in every camera
+    flat = [at(5, 5, 0.7), at(15, 10, 0.7), at(25, 15, 0.7)]                            # named as (A, A, B): area 0 on every screen
+    for tri in (whole, medium, nearer, flat):
+        n = len(v)
+        f.append([n, n, n + 1] if tri is flat else [n, n + 1, n + 2])
+        v += tri
+    v, f = F(v), np.asarray(f, np.int32)
+    assert len(f) == 36 and small == 32
+    # the boxes of the first camera straddle the walkers' threshold of 64 pixels
+    uv = v[:, :2] / v[:, 2:] * focal + F([18.5, 14.5])
+    lo = np.clip(np.floor(uv[f].min(1)), 0, [W - 1, H - 1])
+    hi = np.clip(np.floor(uv[f].max(1)), 0, [W - 1, H - 1])
+    area = np.prod(hi - lo + 1, axis=1)
+    assert (area[:small] <= 64).all() and area[small] == W * H and area[small + 1] > 64
+    views, zb = mesh.vertex_views(to_mesh(v, f), K, poses, (W, H), bias=0.01, near=near, return_zbuffer=True)
+    cull = zb.cpu().numpy().view(np.uint32)
+    assert cull.shape == (3, H, W)
+    u = to_mesh(v, f)
+    u.texture = mesh.texture_atlas(u, 2)
+    u.texture.image = torch.zeros(u.texture.height, u.texture.width, 3, dtype=torch.uint8, device="cuda")
+    a = to_mesh(v, f)
+    painted(a, mesh.texture_atlas(a, texel_size=0.02), 5)
+    assert len(np.unique(AR.face_classes(v, f, 0.02))) >= 3
+    ws = 2 * 8 * W * H                                                                  # two cameras, then one
+    _, uid, udepth = mesh.render_textured(u, K, poses, (W, H), near=near, max_workspace_bytes=ws, return_ids=True)
+    _, aid, adepth = mesh.render_textured(a, K, poses, (W, H), near=near, max_workspace_bytes=ws, return_ids=True)
+    udepth, adepth = udepth.cpu().numpy().view(np.uint32), adepth.cpu().numpy().view(np.uint32)
+    assert np.array_equal(cull, udepth), "%d depth words of the cull and the uniform render differ" % (cull != udepth).sum()
+    assert np.array_equal(cull, adepth), "%d depth words of the cull and the adaptive render differ" % (cull != adepth).sum()
+    uid, aid = uid.cpu().numpy(), aid.cpu().numpy()
+    assert np.array_equal(uid, aid)
+    # the scene is the one described: every pixel is covered, all three kinds of face win pixels, the culled two never do
+    assert (uid >= 0).all() and not np.isin(uid, [small + 2, small + 3]).any()
+    for c in range(3):
+        assert (uid[c] < small).sum() > 100 and (uid[c] == small).sum() > 100 and (uid[c] == small + 1).sum() > 20
+
+
 # ---- 4. no bleeding
 
 

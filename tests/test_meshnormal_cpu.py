@@ -85,7 +85,8 @@ def test_code_object_and_build_entry():
     for rel in build.MESHNORMAL_SOURCES + build.MESHNORMAL_HEADERS:
         assert os.path.exists(os.path.join(build.CSRC, rel)), rel
     source = open(os.path.join(build.CSRC, build.MESHNORMAL_SOURCES[0])).read()
-    assert set(re.findall(r'#include\s*"([^"]+)"', source)) == {"ngp_meshnormal.h"}               # nothing of another library is compiled in
+    # no other library's ABI header or source is compiled in: only the walk's device code, shared with libngp_meshdist.so
+    assert set(re.findall(r'#include\s*"([^"]+)"', source)) == {"ngp_meshnormal.h", "../mesh_nearest.h"}
     assert "constexpr int THREADS = 256;" in source
 
 
