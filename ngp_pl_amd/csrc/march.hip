@@ -563,6 +563,87 @@ __device__ __forceinline__ int march_tile_walk(const Ray& ray, const MarchParams
     return n;
 }
 
+// ------------------------------------------------------------------------------------------
+// Reach table (SIMPLE path, 128^3 grid): which rays, and which tails of rays, cannot meet an occupied cell.
+// any[l], l = (bz << 8) | (by << 4) | bx: some cell of the 8^3 block (bx, by, bz) -- the 512 Morton-consecutive cells from
+// 512 morton(bx, by, bz), render_begin_kernel's test -- is occupied.  reach[l]: the OR of `any` over the block's 27-neighbourhood,
+// clamped at the grid border.  Both in LINEAR order (the pre-test forms block coordinates, not Morton codes), 512 B each.
+// Sixteen workgroups, one per slab bz, no exchange between them: thread (bx, by) ORs the three blocks (bx, by, bz - 1 .. bz + 1) --
+// twelve 16-byte loads in one round trip, the 256 KB bitfield is read three times over from L2 -- and the 3 x 3 neighbourhood in
+// (bx, by) closes over LDS.
+// ------------------------------------------------------------------------------------------
+constexpr int REACH_WORDS = 128;                 // (128 / 8)^3 blocks, one bit each
+__global__ void __launch_bounds__(256)
+march_reach_table_kernel(const uint8_t* __restrict__ bitfield, uint32_t* __restrict__ any_out, uint32_t* __restrict__ reach_out) {
+    __shared__ uint32_t s_col[256];              // [by][bx]: any of the three blocks of the column
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int bx = tid & 15, by = tid >> 4, bz = blockIdx.x;
+    uint4 v[3][4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const uint32_t b = ngp_morton3D((uint32_t)bx, (uint32_t)by, (uint32_t)min(max(bz + k - 1, 0), 15));
+        const uint4* cells = reinterpret_cast<const uint4*>(bitfield) + 4 * (size_t)b;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[k][i] = cells[i];
+    }
+    uint32_t o[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        o[k] = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[k] |= v[k][i].x | v[k][i].y | v[k][i].z | v[k][i].w;
+    }
+    const int l = (bz << 8) | tid;
+    const unsigned long long m_any = __ballot(o[1] != 0u);
+    if (lane == 0) { any_out[l >> 5] = (uint32_t)m_any; any_out[(l >> 5) + 1] = (uint32_t)(m_any >> 32); }
+    s_col[tid] = o[0] | o[1] | o[2];
+    __syncthreads();
+    uint32_t r = 0u;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) r |= s_col[(min(max(by + dy, 0), 15) << 4) | min(max(bx + dx, 0), 15)];
+    const unsigned long long m = __ballot(r != 0u);
+    if (lane == 0) { reach_out[l >> 5] = (uint32_t)m; reach_out[(l >> 5) + 1] = (uint32_t)(m >> 32); }
+}
+
+// The pre-test of the pruned train march (wave-uniform ray, hit interval [t1, t2] BEFORE the jitter): returns the far end the walk
+// needs, t2' <= t2, or a negative value when the ray cannot meet an occupied cell at all.  Lane j tests the point P_j = o + t_j d,
+// t_j = t1 + j step, step = half a block edge in ray parameter, j = 0 .. need - 1 with t_(need-1) at or behind t2, and reads the
+// reach bit of P_j's block (march_probe's normalisation at 16 per axis: v * 16 and v * 128 are the same float scaled by a power of
+// two, so floor(v * 16) is the block coordinate floor(v * 128) >> 3 of the same point).  Why no sample is lost:
+//   1. consecutive test points are half a block apart, so every point of the ray in [t1, t2] is within a quarter block of a test
+//      point (the walk's candidates all lie in [t1 + jitter dt, t2), inside that interval);
+//   2. a candidate the walk could emit has its COMPUTED cell occupied, so that cell's block B has any = 1.  Its nearest test point is
+//      a quarter block away per axis at most, so that point's block coordinates differ from B's by at most one per axis (the clamp
+//      to 0..15 keeps that): B is in the 27-neighbourhood of the test point's block, whose reach bit is therefore set;
+//   3. the roundings -- positions are fmaf(t, d, o) within 1e-7 of the box, step and t_j within 1e-6 relative, the clamp of an index
+//      at the grid border -- move a point by far less than the three quarters of a block (a block is 1/16 of the box) that step 2
+//      leaves unused;
+//   4. so no bit set means no candidate is ever emitted, and with `last` the highest set lane no candidate at
+//      t >= t1 + (last + 1) step is: its nearest test point is behind lane `last` (by half a step, against roundings of 1e-6 steps);
+//   5. the walk then runs from the same t_start on the same lattice with the smaller far end.  That only removes candidates from the
+//      end of the sequence it visits, none of which it would have emitted; every earlier probe, skip and emission is the same;
+//   6. hence n, the cap at max_samples, the scratch row and everything downstream are the same bits.
+// Not pruned (returns t2): a ray that would need more than 62 points (one across the box diagonal needs 57), non-finite inputs.
+__device__ __forceinline__ float march_reach_far(const Ray& ray, const MarchParams& p, const uint32_t* __restrict__ reach, float t1, float t2, int lane) {
+    const float step = (p.bound0 * 0.0625f) / sqrtf(ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz);
+    const float q = (t2 - t1) / step;
+    const float mag = fabsf(ray.ox) + fabsf(ray.oy) + fabsf(ray.oz) + fabsf(ray.dx) + fabsf(ray.dy) + fabsf(ray.dz) + t2;
+    if (!(step > 0.0f && step < 3.0e38f && q >= 0.0f && q < 61.0f && mag < 3.0e38f)) return t2;       // (false for NaN)
+    const int need = (int)q + 2;
+    const float t = fmaf((float)lane, step, t1);
+    const float x = fmaf(t, ray.dx, ray.ox), y = fmaf(t, ray.dy, ray.oy), z = fmaf(t, ray.dz, ray.oz);
+    const int bx = (int)fmaxf(0.0f, fminf(0.5f * (x * p.bound0_inv + 1) * 16.0f, 15.0f));
+    const int by = (int)fmaxf(0.0f, fminf(0.5f * (y * p.bound0_inv + 1) * 16.0f, 15.0f));
+    const int bz = (int)fmaxf(0.0f, fminf(0.5f * (z * p.bound0_inv + 1) * 16.0f, 15.0f));
+    const int l = (bz << 8) | (by << 4) | bx;
+    const unsigned long long m = __ballot(lane < need && ((reach[l >> 5] >> (l & 31)) & 1u) != 0u);
+    if (!m) return -1.0f;
+    const int last = 63 - (int)__builtin_clzll(m);
+    return fminf(t2, fmaf((float)(last + 1), step, t1));
+}
+
 // Pass 1 of train marching, one wave per ray (march_tile_walk); the samples' t go to the ray's scratch row (coalesced).
 // PROLOGUE (the native stepper's march): the wave also forms its ray's hit interval and jitter -- render()'s prologue
 // (rendering.py:27-29: one box, one hit, near clamp; custom_functions.py:83: the jitter draw), the arithmetic of ray_aabb_near_kernel
@@ -573,7 +654,8 @@ __global__ void __launch_bounds__(256)
 march_train_count_wave_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                               const float* __restrict__ hits_t, const float* __restrict__ noise,
                               MarchParams p, int max_samples, int n_rays,
-                              int64_t* __restrict__ rays_a, float* __restrict__ t_scratch, int32_t* __restrict__ counts, MarchPrologue pro) {
+                              int64_t* __restrict__ rays_a, float* __restrict__ t_scratch, int32_t* __restrict__ counts, MarchPrologue pro,
+                              const uint32_t* __restrict__ reach) {
     // the ray index is wave-uniform; saying so keeps the ray, its hit interval and the whole tile walk on the scalar unit
     const int r = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
     const int lane = threadIdx.x & 63;
@@ -590,6 +672,12 @@ march_train_count_wave_kernel(const float* __restrict__ rays_o, const float* __r
         if (lane == 0) { reinterpret_cast<float2*>(pro.hits_out)[r] = make_float2(t1, t2); pro.noise_out[r] = jitter; }
     } else {
         t1 = hits_t[2 * r]; t2 = hits_t[2 * r + 1]; jitter = noise[r];
+    }
+    // reach != nullptr (the native stepper's pruned march, SIMPLE only): no walk for a ray that cannot meet an occupied cell, and none
+    // behind the last place where it can (march_reach_far has the argument); hits_out / noise_out above keep the full interval
+    if (SIMPLE && reach != nullptr && t1 >= 0) {
+        t2 = march_reach_far(ray, p, reach, t1, t2, lane);
+        if (t2 < 0) t1 = -1.0f;
     }
     if (t1 >= 0) t1 = fmaf(calc_dt(t1, p), jitter, t1);
     float* __restrict__ row = t_scratch + (size_t)r * max_samples;
@@ -1214,12 +1302,14 @@ template <typename F> void with_bool(bool flag, F f) { if (flag) f(std::true_typ
 // bit-identical to the serial loop, 101 us instead of 280-330 us per 8192-ray batch: profiles/archive_r01_r04/r01_v20_wave_march_kernel_trace.txt,
 // sweep of round 2: the step time is the same for every placement, the marching stream is busy a third as long).
 // pro != nullptr: the wave forms hits and jitter itself (hits_t, noise unused); else it reads them.
+// reach != nullptr (SIMPLE, 128^3): the reach table of march_reach_table_kernel; rays and ray tails it rules out are not walked.
 void launch_train_count(const float* rays_o, const float* rays_d, const float* hits_t, const float* noise, const MarchParams& p, int max_samples,
-                        int n_rays, int64_t* rays_a, float* t_scratch, int32_t* counts, const MarchPrologue* pro, ngp_stream_t stream) {
+                        int n_rays, int64_t* rays_a, float* t_scratch, int32_t* counts, const MarchPrologue* pro, ngp_stream_t stream,
+                        const uint32_t* reach = nullptr) {
     const dim3 grid(ngp_div_up((long long)n_rays * 64, 256));
     with_bool(p.simple, [&](auto S) { with_bool(pro != nullptr, [&](auto P) {
         hipLaunchKernelGGL((march_train_count_wave_kernel<decltype(S)::value, decltype(P)::value>), grid, dim3(256), 0, ngp_stream(stream),
-                           rays_o, rays_d, hits_t, noise, p, max_samples, n_rays, rays_a, t_scratch, counts, pro ? *pro : MarchPrologue{});
+                           rays_o, rays_d, hits_t, noise, p, max_samples, n_rays, rays_a, t_scratch, counts, pro ? *pro : MarchPrologue{}, reach);
     }); });
 }
 
@@ -1236,6 +1326,28 @@ void launch_train_write(const float* rays_o, const float* rays_d, const int64_t*
 }
 
 }  // namespace
+
+// (csrc/ngp_internal.h, not exported) ngp_march_train_fused with the pruned count: reach_ws != nullptr (2 x REACH_WORDS words of
+// device memory the caller owns) and a SIMPLE configuration on a 128^3 grid put one more launch in front -- the reach table, built
+// from the bitfield THIS call marches through, on the same stream: it cannot be stale whoever wrote the bitfield -- and hand the table
+// to the count kernel.  Any other configuration, or reach_ws == nullptr: exactly ngp_march_train_fused.
+int march_train_fused_reach(const float* rays_o, const float* rays_d, const float* center, const float* half_size,
+                            float near_distance, uint64_t seed, const uint8_t* density_bitfield, int cascades, float scale,
+                            float exp_step_factor, int grid_size, int max_samples, int n_rays,
+                            float* hits_t, float* noise, int64_t* rays_a, int32_t* counts, int32_t* counter, float* t_scratch,
+                            float* xyzs, float* dirs, float* deltas, float* ts, uint32_t* reach_ws, ngp_stream_t stream) {
+    const MarchParams p = make_march_params(density_bitfield, cascades, grid_size, scale, scale, exp_step_factor, max_samples);
+    const MarchPrologue pro = {center, half_size, near_distance, (uint32_t)seed, (uint32_t)(seed >> 32), hits_t, noise};
+    const uint32_t* reach = nullptr;
+    if (reach_ws != nullptr && p.simple && grid_size == 128 && (reinterpret_cast<uintptr_t>(density_bitfield) & 15) == 0) {
+        hipLaunchKernelGGL(march_reach_table_kernel, dim3(16), dim3(256), 0, ngp_stream(stream), density_bitfield, reach_ws, reach_ws + REACH_WORDS);
+        reach = reach_ws + REACH_WORDS;
+    }
+    launch_train_count(rays_o, rays_d, nullptr, nullptr, p, max_samples, n_rays, rays_a, t_scratch, counts, &pro, stream, reach);
+    launch_train_write(rays_o, rays_d, rays_a, t_scratch, scale, exp_step_factor, grid_size, max_samples, n_rays, xyzs, dirs, deltas, ts,
+                       0, nullptr, nullptr, nullptr, counts, rays_a, counter, stream);
+    return NGP_LAUNCH_RESULT();
+}
 
 // ------------------------------------------------------------------------------------------
 // C ABI
@@ -1415,12 +1527,9 @@ int ngp_march_train_fused(const float* rays_o, const float* rays_d, const float*
     NGP_CHECK_PTR(hits_t); NGP_CHECK_PTR(noise); NGP_CHECK_PTR(rays_a); NGP_CHECK_PTR(counts); NGP_CHECK_PTR(counter); NGP_CHECK_PTR(t_scratch);
     NGP_CHECK_PTR(xyzs); NGP_CHECK_PTR(dirs); NGP_CHECK_PTR(deltas); NGP_CHECK_PTR(ts);
     if (reinterpret_cast<uintptr_t>(counts) & 15) return NGP_EINVAL;               // (the prefix reads it 16 bytes at a time)
-    const MarchParams p = make_march_params(density_bitfield, cascades, grid_size, scale, scale, exp_step_factor, max_samples);
-    const MarchPrologue pro = {center, half_size, near_distance, (uint32_t)seed, (uint32_t)(seed >> 32), hits_t, noise};
-    launch_train_count(rays_o, rays_d, nullptr, nullptr, p, max_samples, n_rays, rays_a, t_scratch, counts, &pro, stream);
-    launch_train_write(rays_o, rays_d, rays_a, t_scratch, scale, exp_step_factor, grid_size, max_samples, n_rays, xyzs, dirs, deltas, ts,
-                       0, nullptr, nullptr, nullptr, counts, rays_a, counter, stream);
-    return NGP_LAUNCH_RESULT();
+    return march_train_fused_reach(rays_o, rays_d, center, half_size, near_distance, seed, density_bitfield, cascades, scale, exp_step_factor,
+                                   grid_size, max_samples, n_rays, hits_t, noise, rays_a, counts, counter, t_scratch, xyzs, dirs, deltas, ts,
+                                   nullptr, stream);
 }
 
 int ngp_raymarching_train_write_k(const float* rays_o, const float* rays_d, const int64_t* rays_a,

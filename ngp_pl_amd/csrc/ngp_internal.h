@@ -265,5 +265,15 @@ int ngp_hashgrid_bwd(const float* x, const float* xyz_min, const float* xyz_max,
 
 #ifdef __cplusplus
 }
+/* Not exported (only csrc/stepper.hip calls it): ngp_march_train_fused whose count kernel skips the rays, and the tails of rays, that
+ * cannot reach an occupied cell -- same outputs, bit for bit (csrc/march.hip, march_reach_far).  reach_ws: 256 x u32 of device memory
+ * for the two 16^3-bit tables a launch in front of the count builds from density_bitfield on every call; NULL, or a configuration
+ * other than one cascade with exp_step_factor 0 on a 128^3 grid: exactly ngp_march_train_fused. */
+__attribute__((visibility("hidden")))
+int march_train_fused_reach(const float* rays_o, const float* rays_d, const float* center, const float* half_size,
+                            float near_distance, uint64_t seed, const uint8_t* density_bitfield, int cascades, float scale,
+                            float exp_step_factor, int grid_size, int max_samples, int n_rays,
+                            float* hits_t, float* noise, int64_t* rays_a, int32_t* counts, int32_t* counter, float* t_scratch,
+                            float* xyzs, float* dirs, float* deltas, float* ts, uint32_t* reach_ws, ngp_stream_t stream);
 #endif
 #endif

@@ -73,6 +73,9 @@ struct ngp_stepper {
     bool expanded[2] = {false, false};    // record set k: its samples are already written (by the march, on its stream)
     int32_t* counts[2] = {nullptr, nullptr};   // per record set: the rays' sample counts as a dense i32 array (ngp_march_train_fused's prefix input)
     int counts_rays = 0;
+    // pruned march (csrc/march.hip, march_reach_far): the two 16^3-bit tables every fused march of a SIMPLE configuration rebuilds from
+    // the bitfield in front of its count kernel; NULL with NGP_MARCH_PRUNE=0 (read at creation: A/B runs, tests)
+    uint32_t* reach_ws = nullptr;
     bool same_stream[2] = {false, false};  // record set k was marched on the main stream itself (render() without a next batch)
     // overflow guard of the native step (GradScaler's skip, train.py:274): two device flags used alternately; the field backward of
     // a step raises guard[guard_parity] when a weight-gradient sum is not finite, the optimizer launch of that step reads it
@@ -200,14 +203,17 @@ int do_march(ngp_stepper* s, const float* rays_o, const float* rays_d, hipStream
     constexpr int FUSED_MARCH_MAX_RAYS = 32768;
     if (s->two_sample_sets && !lists_wanted && b.n_rays <= FUSED_MARCH_MAX_RAYS) {
         // TWO launches: prologue + count, prefix + expansion into this record set's own sample buffers (the running step reads the
-        // other set).  The count reaches the pinned word from the second launch's last workgroup before it expands.
+        // other set).  The count reaches the pinned word from the second launch's last workgroup before it expands.  A SIMPLE
+        // configuration (one cascade, constant step) gets a third launch in front, the reach table of the pruned count, built from the
+        // bitfield on every call: never stale, whoever wrote the bitfield since the last march.
         STEP_TRY(ensure_counts(s));
         const ngp_stepper::SampleSet& w = s->samples[k];
         s->set_k[k] = 0;
-        STEP_TRY(ngp_march_train_fused(rays_o, rays_d, c.center, c.half_size, c.near_distance, c.noise_seed + 0x9E3779B97F4A7C15ull * (++s->marches),
-                                       c.density_bitfield, c.cascades, c.scale, c.exp_step_factor, c.grid_size, c.max_samples, b.n_rays,
-                                       b.hits_t[k], b.noise[k], b.rays_a[k], s->counts[k], b.counter[k], b.scratch[k],
-                                       w.xyzs, w.dirs, w.deltas, w.ts, (ngp_stream_t)side));
+        const bool simple = c.cascades == 1 && c.exp_step_factor == 0.0f;
+        STEP_TRY(march_train_fused_reach(rays_o, rays_d, c.center, c.half_size, c.near_distance, c.noise_seed + 0x9E3779B97F4A7C15ull * (++s->marches),
+                                         c.density_bitfield, c.cascades, c.scale, c.exp_step_factor, c.grid_size, c.max_samples, b.n_rays,
+                                         b.hits_t[k], b.noise[k], b.rays_a[k], s->counts[k], b.counter[k], b.scratch[k],
+                                         w.xyzs, w.dirs, w.deltas, w.ts, simple ? s->reach_ws : nullptr, (ngp_stream_t)side));
         s->expanded[k] = true;
         s->fused[k] = true;
         if (s->timing) { STEP_HIP(hipEventRecord(s->march_t[k][1], side)); s->march_t_set[k] = true; }
@@ -282,6 +288,8 @@ int ngp_stepper_create(const ngp_stepper_config* config, const ngp_step_buffers*
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->guard), 2 * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(s->guard, 0, 2 * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->scaler_state), 4 * sizeof(float));
+    const char* prune = getenv("NGP_MARCH_PRUNE");
+    if (e == hipSuccess && !(prune && strcmp(prune, "0") == 0)) e = hipMalloc(reinterpret_cast<void**>(&s->reach_ws), 256 * sizeof(uint32_t));
     if (e != hipSuccess) { ngp_stepper_destroy(s); return (int)e; }
     *out = s;
     return 0;
@@ -299,6 +307,7 @@ int ngp_stepper_destroy(ngp_stepper* s) {
     for (int k = 0; k < 2; ++k) if (s->counts[k]) (void)hipFree(s->counts[k]);
     if (s->guard) (void)hipFree(s->guard);
     if (s->scaler_state) (void)hipFree(s->scaler_state);
+    if (s->reach_ws) (void)hipFree(s->reach_ws);
     destroy_exchange_events(s);
     delete s;
     return 0;
