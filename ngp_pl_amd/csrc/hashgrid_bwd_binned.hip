@@ -66,14 +66,11 @@ constexpr int MAX_CHUNKS = 4608;             // 4.7 M samples: the first steps o
 #ifndef NGP_APPLY_B
 #define NGP_APPLY_B 11
 #endif
-#ifndef NGP_APPLY_WRITEOUT_BATCHED
-#define NGP_APPLY_WRITEOUT_BATCHED 0          // accumulators per thread read together at write-out; 0: one at a time (round 2; A/B builds)
-#endif
-#ifndef NGP_DIR_BY_WAVE0
-#define NGP_DIR_BY_WAVE0 1                    // 0: every thread fetches its part of the next directory row under the write-out (rounds 4-6; A/B builds)
-#endif
 #ifndef NGP_DENSE_B
 #define NGP_DENSE_B 2                         // dense levels: entries per lane in flight (round 6, same box: 2 -> 122.8 us alone, 4 -> 125.6, 8 -> 128.7)
+#endif
+#ifndef NGP_DENSE_K_BIG
+#define NGP_DENSE_K_BIG 4                     // dense levels with more than two slices: tasks per slice (make_plan)
 #endif
 constexpr int APPLY_THREADS = NGP_APPLY_THREADS;
 
@@ -85,7 +82,6 @@ struct BinPlan {
     int32_t order[NGP_MAX_LEVELS];           // levels, most expensive tasks first
     int64_t part_off[NGP_MAX_LEVELS];        // K-split levels: entry offset of the level's K partial tables in ws.partial
     int64_t pool_off[NGP_MAX_LEVELS];        // the level's list slots in ws.pool, in 4-byte words
-    int32_t entry_words[NGP_MAX_LEVELS];     // words per list entry: 1 = sample id (dense levels), 3 = payload entry (hashed levels)
     int32_t n_tasks, n_chunks;
 };
 
@@ -191,7 +187,7 @@ bin_kernel(const float* __restrict__ x, const float* __restrict__ xyz_min, const
         if (threadIdx.x == 0) s_pre[ns] = run;
     }
     __syncthreads();
-    int32_t* __restrict__ slot = ws.pool + plan.pool_off[level] + (size_t)chunk * CHUNK_SLOTS * plan.entry_words[level];
+    int32_t* __restrict__ slot = ws.pool + plan.pool_off[level] + (size_t)chunk * CHUNK_SLOTS;
     {
 #pragma unroll
         for (int t = 0; t < BIN_SPT; ++t)
@@ -220,39 +216,7 @@ __device__ __forceinline__ void lds_add_fixed(long long* acc, float v) {
     atomicAdd(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)fix_q64(v));   // ds_add_u64
 }
 
-// One pass for the lanes of a wave over whole-sample entries (dense levels): all 8 corners, in-slice test each.
-template <int B>
-__device__ __forceinline__ void apply_entries(long long* lds, uint32_t lo, uint32_t len, uint32_t res, uint32_t size, float scale,
-                                              const float* __restrict__ x, const Box& box, const half2_t* __restrict__ g_level,
-                                              const int32_t* __restrict__ active, const int (&ee)[B], const bool (&ok)[B]) {
-    int src[B]; half2_t g[B]; float px[B][3];
-#pragma unroll
-    for (int b = 0; b < B; ++b) { const int jj = ee[b] >> 2; g[b] = g_level[jj]; src[b] = active ? active[jj] : jj; }
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-        const float* __restrict__ xp = x + 3 * (size_t)src[b];
-        px[b][0] = xp[0]; px[b][1] = xp[1]; px[b][2] = xp[2];
-    }
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-        if (!ok[b]) continue;
-        const float g0 = (float)g[b][0], g1 = (float)g[b][1];
-        uint32_t p[3], idx[8]; float f[3];
-        cell_of_loaded(px[b], box, scale, p, f);
-        corner_indices<false>(p, res, size, idx);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const uint32_t local = idx[c] - lo;
-            if (local < len) {
-                const float w = corner_weight(c, f);
-                lds_add_fixed(lds + 2 * local, w * g0);
-                lds_add_fixed(lds + 2 * local + 1, w * g1);
-            }
-        }
-    }
-}
-
-// The same for (sample, corner pair) entries of a hashed level: entry = (j << 2) | (cy + 2 cz); only the pair
+// One pass for the lanes of a wave over (sample, corner pair) entries of a hashed level: entry = (j << 2) | (cy + 2 cz); only the pair
 // (x, y+cy, z+cz), (x+1, y+cy, z+cz) is formed -- index arithmetic and weight order of corner_indices()/corner_weight().
 template <int B>
 __device__ __forceinline__ void apply_pairs(long long* lds, uint32_t lo, uint32_t len, uint32_t size, float scale,
@@ -320,39 +284,11 @@ __device__ __forceinline__ void apply_segments_hashed(long long* lds, uint32_t l
 // samples of a ray sit in the same cell, i.e. consecutive entries hit the same 8 accumulators
 // (measured: an LDS add_u64 with 8 lanes per address costs 64 cycles instead of 11.5).  Lane L
 // therefore walks the contiguous run [L*R, (L+1)*R) of the segment: the lanes of a wave are a whole
-// run apart, on different rays.
-#ifndef NGP_DENSE_RUNS
-#define NGP_DENSE_RUNS 1                 // 0: every sample's 16 updates go to LDS one by one (round 2; kept for A/B builds)
-#endif
-template <int B>
-__device__ __forceinline__ void apply_segments_dense(long long* lds, uint32_t lo, uint32_t len, uint32_t res, uint32_t size, float scale,
-                                                     const float* __restrict__ x, const Box& box, const half2_t* __restrict__ g_level,
-                                                     const int32_t* __restrict__ active, const int32_t* __restrict__ pool_level,
-                                                     const int* s_dir, int n_chunks, int part, int K) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int NW = APPLY_THREADS / 64;
-    for (int c = part + K * wave; c < n_chunks; c += K * NW) {
-        const int d = s_dir[c];
-        const int cnt = d & 0xffff;
-        const size_t start = (size_t)c * CHUNK_SLOTS + (d >> 16);
-        const int R = (cnt + 63) >> 6;
-        for (int t0 = 0; t0 < R; t0 += B) {
-            int jj[B]; bool ok[B];
-#pragma unroll
-            for (int b = 0; b < B; ++b) {
-                const int i = lane * R + t0 + b;
-                ok[b] = (t0 + b < R) && i < cnt;
-                jj[b] = ok[b] ? pool_level[start + i] : 0;
-            }
-            apply_entries<B>(lds, lo, len, res, size, scale, x, box, g_level, active, jj, ok);
-        }
-    }
-}
-
-// Within a lane's run consecutive entries are consecutive samples of a ray (a chunk's list keeps the order in which the
-// binning waves arrived: blocks of 64 consecutive samples), i.e. they sit in the same cell for 10-40 steps on the coarse
-// levels: the 8 corner sums are kept in REGISTERS -- as 64-bit fixed point, the accumulators' own arithmetic: exact, so
-// neither the run boundaries nor the list order can change a bit of the result -- and reach LDS when the cell changes.
+// run apart, on different rays.  Within a lane's run consecutive entries are consecutive samples of a
+// ray (a chunk's list keeps the order in which the binning waves arrived: blocks of 64 consecutive
+// samples), i.e. they sit in the same cell for 10-40 steps on the coarse levels: the 8 corner sums are
+// kept in REGISTERS -- as 64-bit fixed point, the accumulators' own arithmetic: exact, so neither the
+// run boundaries nor the list order can change a bit of the result -- and reach LDS when the cell changes.
 __device__ __forceinline__ void flush_cell(long long* lds, uint32_t lo, uint32_t len, uint32_t res, uint32_t size, uint32_t key,
                                            const long long (&acc)[16]) {
     const uint32_t r2 = res * res;
@@ -368,10 +304,10 @@ __device__ __forceinline__ void flush_cell(long long* lds, uint32_t lo, uint32_t
     }
 }
 template <int B>
-__device__ __forceinline__ void apply_segments_dense_runs(long long* lds, uint32_t lo, uint32_t len, uint32_t res, uint32_t size, float scale,
-                                                          const float* __restrict__ x, const Box& box, const half2_t* __restrict__ g_level,
-                                                          const int32_t* __restrict__ active, const int32_t* __restrict__ pool_level,
-                                                          const int* s_dir, int n_chunks, int part, int K) {
+__device__ __forceinline__ void apply_segments_dense(long long* lds, uint32_t lo, uint32_t len, uint32_t res, uint32_t size, float scale,
+                                                     const float* __restrict__ x, const Box& box, const half2_t* __restrict__ g_level,
+                                                     const int32_t* __restrict__ active, const int32_t* __restrict__ pool_level,
+                                                     const int* s_dir, int n_chunks, int part, int K) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int NW = APPLY_THREADS / 64;
     const uint32_t top = res - 1u, r2 = res * res;
@@ -436,7 +372,6 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // (Applying the hashed levels' Adam update in this kernel's write-out -- three designs, the last with wave specialisation -- was built and
 // measured in round 4: the optimizer's stream is not hidden under the owners' latencies, the owners slow down by as much as the stream takes
 // alone; removed in round 5.  profiles/archive_r01_r04/r04_step_ab.txt (d), (d2).)
-template <bool UNUSED>       // (the template argument only keeps the kernel's name in the round 3-4 traces: apply_kernel<false>)
 __global__ void __launch_bounds__(APPLY_THREADS, NGP_APPLY_WAVES_PER_EU)
 apply_kernel(const float* __restrict__ x, const float* __restrict__ xyz_min, const float* __restrict__ xyz_max,
              const half2_t* __restrict__ dfeats, GridMeta meta, BinPlan plan, BinWs ws, int n_samples,
@@ -454,11 +389,10 @@ apply_kernel(const float* __restrict__ x, const float* __restrict__ xyz_min, con
     const int n_chunks = min(plan.n_chunks, (n_live + CHUNK - 1) / CHUNK);
     const int tid = threadIdx.x;
     // TWO barriers per task, none of them behind a global round trip (round 4; three before, the first behind the load of the
-    // task's directory row): the id of task k+1 is requested from the queue at the top of task k and published at the barrier
-    // behind task k's accumulation; its directory row is then loaded into registers, rides under task k's write-out and is
-    // parked in the other half of s_dir2 at the closing barrier.  The accumulators are cleared by the write-out pass that
-    // reads them (the first task finds them cleared by the prologue).
-    constexpr int PRE = (MAX_CHUNKS + APPLY_THREADS - 1) / APPLY_THREADS;
+    // task's directory row): the id of task k+1 is requested from the queue at the top of task k; wave 0 copies that task's
+    // directory row into the other half of s_dir2 as soon as its own share of task k's accumulation is done, and the barrier
+    // behind the accumulation publishes both.  The accumulators are cleared by the write-out pass that reads them (the first
+    // task finds them cleared by the prologue).
     auto dir_row = [&](int task_id) -> const int32_t* {
         int oi = 0;
         while (task_id >= plan.first_task[oi + 1]) ++oi;
@@ -500,15 +434,14 @@ apply_kernel(const float* __restrict__ x, const float* __restrict__ xyz_min, con
 #endif
         const half2_t* __restrict__ g_level = dfeats + (size_t)level * n_samples;
         const int32_t* __restrict__ pool_level = ws.pool + plan.pool_off[level];
-        if (level_is_hashed(res, size)) {
+        if (level_is_hashed(res, size))
             apply_segments_hashed<NGP_APPLY_B>(lds, lo, len, res, size, meta.scale[level], x, box, g_level, active, pool_level, s_dir, n_chunks, part, K);
-        }
-        else if (NGP_DENSE_RUNS) apply_segments_dense_runs<NGP_DENSE_B>(lds, lo, len, res, size, meta.scale[level], x, box, g_level, active, pool_level, s_dir, n_chunks, part, K);
-        else apply_segments_dense<4>(lds, lo, len, res, size, meta.scale[level], x, box, g_level, active, pool_level, s_dir, n_chunks, part, K);
-#if NGP_DIR_BY_WAVE0
+        else
+            apply_segments_dense<NGP_DENSE_B>(lds, lo, len, res, size, meta.scale[level], x, box, g_level, active, pool_level, s_dir, n_chunks, part, K);
         // The next task's directory row is fetched by WAVE 0 alone, as soon as its own rows are done and before the barrier: the global
-        // round trip hides in the other waves' remaining rows (the waves of a task finish microseconds apart) instead of sitting in the
-        // write-out, where all sixteen waited for it (round 6: 3 us of a 20 us task).  The row goes straight into the idle half of s_dir2.
+        // round trip hides in the other waves' remaining rows (the waves of a task finish microseconds apart).  (Every thread fetching its
+        // part of the row under the write-out, rounds 4-6, had all sixteen waves wait for it there: 3 us of a 20 us task.)  The row goes
+        // straight into the idle half of s_dir2.
         if (tid < 64) {
             const int nt0 = __shfl(next_task, 0, 64);                  // (thread 0 holds the id the queue returned)
             if (tid == 0) s_task[(it + 1) & 1] = nt0;
@@ -524,71 +457,19 @@ apply_kernel(const float* __restrict__ x, const float* __restrict__ xyz_min, con
                 }
             }
         }
-#else
-        if (tid == 0) s_task[(it + 1) & 1] = next_task;
-#endif
-        lds_barrier();                                                 // accumulators complete, next id visible
+        lds_barrier();                                                 // accumulators complete, next id and its directory row visible
 #ifdef NGP_BIN_TIMING
         if (tid == 0) ws.timing[4 * task + 2] = (long long)wall_clock64();
 #endif
-#if !NGP_DIR_BY_WAVE0
-        const int nt = s_task[(it + 1) & 1];
-        int pre[PRE];
-        if (nt < task_end) {                                           // (uniform) the next task's directory row, in flight under the write-out
-            const int32_t* __restrict__ dn = dir_row(nt);
-#pragma unroll
-            for (int q = 0; q < PRE; ++q) { const int c = tid + q * APPLY_THREADS; pre[q] = c < n_chunks ? dn[c] : 0; }
-        }
-#endif
         half2_t* __restrict__ out = grad_table + meta.offset[level] + lo;
         const float inv = 1.0f / FIX_SCALE;
-#if NGP_APPLY_WRITEOUT_BATCHED
-        {
-            // all of a thread's accumulators are read (16-byte LDS reads), then cleared, then converted and stored: the reads of one
-            // entry do not wait behind the clear of the previous one (same array: the compiler keeps them in program order)
-            typedef long long ll2 __attribute__((ext_vector_type(2)));
-            constexpr int WO = (int)((SLICE2 + APPLY_THREADS - 1) / APPLY_THREADS), WB = NGP_APPLY_WRITEOUT_BATCHED;
-            float2* __restrict__ pout = ws.partial + plan.part_off[level] + (size_t)part * size + lo;
-            const ll2 z2 = {0, 0};
-#pragma unroll
-            for (int q0 = 0; q0 < WO; q0 += WB) {
-                ll2 acc2[WB];
-#pragma unroll
-                for (int q = 0; q < WB; ++q) {
-                    const uint32_t k = tid + (q0 + q) * APPLY_THREADS;
-                    acc2[q] = *reinterpret_cast<const ll2*>(lds + 2 * (k < len ? k : 0));
-                }
-#pragma unroll
-                for (int q = 0; q < WB; ++q) {
-                    const uint32_t k = tid + (q0 + q) * APPLY_THREADS;
-                    if (k < len) *reinterpret_cast<ll2*>(lds + 2 * k) = z2;               // ready for the next task
-                }
-#pragma unroll
-                for (int q = 0; q < WB; ++q) {
-                    const uint32_t k = tid + (q0 + q) * APPLY_THREADS;
-                    if (k < len) {
-                        const float a0 = (float)acc2[q][0] * inv, a1 = (float)acc2[q][1] * inv;
-                        if (K == 1) { half2_t v; v[0] = sat_f16(a0); v[1] = sat_f16(a1); out[k] = v; }
-                        else pout[k] = make_float2(a0, a1);
-                    }
-                }
-            }
-        }
-#else
         for (uint32_t k = tid; k < len; k += APPLY_THREADS) {
             const float a0 = (float)lds[2 * k] * inv, a1 = (float)lds[2 * k + 1] * inv;
             lds[2 * k] = 0; lds[2 * k + 1] = 0;                        // ready for the next task
             if (K == 1) { half2_t v; v[0] = sat_f16(a0); v[1] = sat_f16(a1); out[k] = v; }
             else ws.partial[plan.part_off[level] + (size_t)part * size + lo + k] = make_float2(a0, a1);
         }
-#endif
-#if !NGP_DIR_BY_WAVE0
-        if (nt < task_end) {
-#pragma unroll
-            for (int q = 0; q < PRE; ++q) { const int c = tid + q * APPLY_THREADS; if (c < n_chunks) s_dir2[(it + 1) & 1][c] = pre[q]; }
-        }
-#endif
-        lds_barrier();                                                 // accumulators clear, the next task's directory row in place (the write-out's stores still in flight)
+        lds_barrier();                                                 // accumulators clear (the write-out's stores still in flight)
 #ifdef NGP_BIN_TIMING
         if (tid == 0) ws.timing[4 * task + 3] = (long long)wall_clock64();
 #endif
@@ -632,9 +513,6 @@ bool make_plan(const ngp_grid_meta* meta, int n_samples, BinPlan& P, BinLayout& 
         const bool hashed = (uint64_t)res * res * res > size;
         const int ns = (int)((size + SLICE2 - 1) / SLICE2);
         P.n_slices[l] = ns;
-#ifndef NGP_DENSE_K_BIG
-#define NGP_DENSE_K_BIG 4
-#endif
         P.k_split[l] = hashed ? 1 : (ns == 1 ? 16 : ns == 2 ? 8 : NGP_DENSE_K_BIG);      // dense: a z-slab can hold most of the scene's samples (64/ns tasks measured slower)
         // relative cost of one task: a dense slice (a slab of the grid) gets all 8 corners of its samples, a hashed one ~2
         cost[l] = hashed ? 1.0 : 4.0;
@@ -656,13 +534,10 @@ bool make_plan(const ngp_grid_meta* meta, int n_samples, BinPlan& P, BinLayout& 
         L.merge_entries += size;
     }
     long long pool_words = 0;
-    for (int l = 0; l < NGP_MAX_LEVELS; ++l) { P.pool_off[l] = 0; P.entry_words[l] = 1; }
-    for (int l = 0; l < meta->n_levels; ++l) {
-        const uint32_t size = meta->offset[l + 1] - meta->offset[l], res = meta->resolution[l];
-        const bool hashed = (uint64_t)res * res * res > size;
-        P.entry_words[l] = 1;
+    for (int l = 0; l < NGP_MAX_LEVELS; ++l) P.pool_off[l] = 0;
+    for (int l = 0; l < meta->n_levels; ++l) {                    // one 4-byte word per list entry
         P.pool_off[l] = pool_words;
-        pool_words += (long long)P.n_chunks * CHUNK_SLOTS * P.entry_words[l];
+        pool_words += (long long)P.n_chunks * CHUNK_SLOTS;
     }
     L.queue = 0;
     L.timing = 256;                               // 2048 tasks x 4 x 8 B (NGP_BIN_TIMING builds)
@@ -751,7 +626,7 @@ static int binned_group_impl(const float* x, const float* xyz_min, const float* 
     (void)hipGetDevice(&dev);
     dev &= 63;
     if (!attr_set[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(apply_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
         if (e != hipSuccess) return (int)e;
         attr_set[dev] = true;
     }
@@ -761,7 +636,7 @@ static int binned_group_impl(const float* x, const float* xyz_min, const float* 
     const int n_tasks = task_end - task_begin;
     if (n_tasks > 0) {
         const int n_wg = n_tasks < NGP_APPLY_WGS ? n_tasks : NGP_APPLY_WGS;
-        apply_kernel<false><<<dim3(n_wg), dim3(APPLY_THREADS), smem, st>>>(
+        apply_kernel<<<dim3(n_wg), dim3(APPLY_THREADS), smem, st>>>(
                 x, xyz_min, xyz_max, (const half2_t*)dfeats, dm, P, ws, n_samples, active_idx, n_active, (half2_t*)grad_table, group, task_begin, task_end);
     }
     if (partials_out != nullptr) {

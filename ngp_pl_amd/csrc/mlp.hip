@@ -39,21 +39,10 @@ constexpr int PAD = 8;           // halves of row padding in LDS
 constexpr int WAVES = 4;         // waves per workgroup
 // backward: waves per workgroup, one workgroup per CU.  Two hidden layers: 128 accumulator registers and 20 KB of LDS image per
 // wave -> 4 waves, one per SIMD.  One hidden layer (the density net): 64 accumulators, 228 registers in all, 12 KB of image ->
-// 8 waves, two per SIMD, which hide each other's LDS / MFMA latencies.
-#ifndef NGP_MLP_BWD_WAVES_1HIDDEN
-#define NGP_MLP_BWD_WAVES_1HIDDEN 8
-#endif
-// Two hidden layers at 8 waves (round 3, NGP_MLP_BWD_WAVES_2HIDDEN=4 builds the round-2 kernel): the operand image shrinks to 7
-// blocks per wave (14 KB instead of 20: the first layer's operands go where the upper layers' have been read), the dW reduction
-// takes the 64-row layers in two 32-row passes (8 x 8 KB of slabs instead of 8 x 16 KB), and the register allocation is held to
-// 256 by the 512-thread launch bound.
-#ifndef NGP_MLP_BWD_WAVES_2HIDDEN
-#define NGP_MLP_BWD_WAVES_2HIDDEN 4
-#endif
+// 8 waves, two per SIMD, which hide each other's LDS / MFMA latencies.  (Two hidden layers at 8 waves, with a 7-block operand
+// image and the dW reduction in 32-row passes, was tried and not adopted: profiles/archive_r01_r04/r03_mlp_bwd_experiments.txt.)
 template <int N_IN, int N_HIDDEN>
-constexpr int bwd_waves() { return N_IN > 32 ? 4 : (N_HIDDEN == 1 ? NGP_MLP_BWD_WAVES_1HIDDEN : NGP_MLP_BWD_WAVES_2HIDDEN); }
-template <int N_IN, int N_HIDDEN>
-constexpr bool bwd_staged() { return N_HIDDEN == 2 && bwd_waves<N_IN, N_HIDDEN>() > 4; }
+constexpr int bwd_waves() { return N_IN > 32 ? 4 : (N_HIDDEN == 1 ? 8 : 4); }
 constexpr int TILE = 32;         // samples per wave tile
 
 __device__ __forceinline__ f32x16 mfma(half8_t a, half8_t b, f32x16 c) {
@@ -113,25 +102,6 @@ __device__ __forceinline__ half8_t relu_bwd(half8_t d, half8_t h) {
         db[k] &= m;
     }
     return __builtin_bit_cast(half8_t, db);
-}
-
-// Stage a (rows, cols) row-major f16 matrix from global into LDS with padded pitch, optionally
-// transposed (LDS gets (cols, rows)).  Whole workgroup participates; 16-byte global loads (cols is a multiple of 8, blobs are
-// 16 B aligned).  Transposed: consecutive lanes take consecutive ROWS, so the eight 2-byte stores of a lane's chunk land on
-// consecutive halves across the wave (lanes on consecutive columns put 16 lanes on one bank).
-__device__ __forceinline__ void stage_weights(const h1* __restrict__ g, h1* lds, int rows, int cols, bool transpose) {
-    const int n8 = rows * cols / 8, chunks = cols / 8;
-    for (int t = threadIdx.x; t < n8; t += blockDim.x) {
-        if (transpose) {
-            const int r = t % rows, c = 8 * (t / rows);
-            const half8_t v = *reinterpret_cast<const half8_t*>(g + r * cols + c);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) lds[(c + e) * (rows + PAD) + r] = v[e];
-        } else {
-            const int r = t / chunks, c = 8 * (t - r * chunks);
-            *reinterpret_cast<half8_t*>(lds + r * (cols + PAD) + c) = *reinterpret_cast<const half8_t*>(g + 8 * t);
-        }
-    }
 }
 
 // ---- SH degree 4 (tiny-cuda-nn spherical_harmonics.h, constants as SURVEY.md section 8a) ----
@@ -234,24 +204,13 @@ struct LdsW {
     static constexpr int G_SIZE = G_WO + 16 * HID;
 };
 
-template <int N_IN, int N_HIDDEN>
+// Forward kernels: the image above from ONE pass over the (tight) blob (cols is a multiple of 8, blobs are 16 B aligned): all of a
+// thread's 16-byte loads issued first -- compile-time trip count, fully coalesced -- then the stores into the padded rows: one global
+// round trip at the head of the kernel.  (Matrix by matrix, a strided loop each, it was three to six dependent ones: 3-4 us of the
+// 26 us field forward.)  THREADS = the workgroup's size.
+template <int N_IN, int N_HIDDEN, int THREADS>
 __device__ __forceinline__ void stage_fwd_weights(const h1* __restrict__ w, h1* lds) {
     using L = LdsW<N_IN, N_HIDDEN>;
-    stage_weights(w, lds + L::OFF_W0, HID, N_IN, false);
-    if (N_HIDDEN == 2) stage_weights(w + L::G_W1, lds + L::OFF_W1, HID, HID, false);
-    stage_weights(w + L::G_WO, lds + L::OFF_WO, 16, HID, false);
-}
-
-// The same image from ONE pass over the (tight) blob: all of a thread's 16-byte loads issued first -- compile-time trip count, fully
-// coalesced -- then the stores into the padded rows: one global round trip at the head of the kernel instead of one per matrix and
-// loop trip (three to six dependent ones: 3-4 us of the 26 us field forward).  THREADS = the workgroup's size.
-#ifndef NGP_MLP_FWD_STAGE_ONCE
-#define NGP_MLP_FWD_STAGE_ONCE 1          // 0: matrix by matrix (A/B builds)
-#endif
-template <int N_IN, int N_HIDDEN, int THREADS>
-__device__ __forceinline__ void stage_fwd_weights_once(const h1* __restrict__ w, h1* lds) {
-    using L = LdsW<N_IN, N_HIDDEN>;
-    if (!NGP_MLP_FWD_STAGE_ONCE) { stage_fwd_weights<N_IN, N_HIDDEN>(w, lds); return; }
     constexpr int C0 = HID * N_IN / 8, C1 = (N_HIDDEN == 2 ? HID * HID / 8 : 0), CO = 16 * HID / 8, CT = C0 + C1 + CO;   // 16-byte chunks
     constexpr int PER = (CT + THREADS - 1) / THREADS;
     half8_t v[PER];
@@ -274,12 +233,11 @@ __device__ __forceinline__ void stage_fwd_weights_once(const h1* __restrict__ w,
 }
 
 // Backward kernels: the forward-layout copy AND the transposed copy of every matrix from ONE pass over the blob -- all of a thread's
-// 16-byte global loads issued first (compile-time trip count), then the stores: one global round trip in the kernel's prologue instead of the
-// seven dependent ones of stage_fwd_weights() + three stage_weights(transpose) calls (the prologue was 15 % / 29 % of the colour / density
-// kernel at the bench's operating point, tools/bench_mlp.py with -DNGP_MLP_TIMING).  Same LDS images bit for bit.
-#ifndef NGP_MLP_STAGE_ONCE
-#define NGP_MLP_STAGE_ONCE 1
-#endif
+// 16-byte global loads issued first (compile-time trip count), then the stores: one global round trip in the kernel's prologue.  (Matrix by
+// matrix and copy by copy it was seven dependent ones: the prologue was 15 % / 29 % of the colour / density kernel at the bench's operating
+// point, tools/bench_mlp.py with -DNGP_MLP_TIMING.)
+// For the transposed copy (LDS gets (cols, rows)) consecutive lanes take consecutive ROWS of a matrix, so the eight 2-byte stores of a
+// lane's chunk land on consecutive halves across the wave (lanes on consecutive columns put 16 lanes on one bank).
 template <int N_IN, int N_HIDDEN, int THREADS>
 __device__ __forceinline__ void stage_bwd_weights(const h1* __restrict__ w, h1* lds, int off_t0, int off_t1, int off_to) {
     using L = LdsW<N_IN, N_HIDDEN>;
@@ -289,7 +247,7 @@ __device__ __forceinline__ void stage_bwd_weights(const h1* __restrict__ w, h1* 
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         const int t = (int)threadIdx.x + k * THREADS;
-        // chunk t of the blob: matrix m (rows x cols), chunk tm inside it; lanes on consecutive ROWS (see stage_weights)
+        // chunk t of the blob: matrix m (rows x cols), chunk tm inside it; lanes on consecutive ROWS (see above)
         int rows, cols, tm, gbase;
         if (t < C0) { rows = HID; cols = N_IN; tm = t; gbase = 0; }
         else if (t < C0 + C1) { rows = HID; cols = HID; tm = t - C0; gbase = L::G_W1; }
@@ -358,7 +316,7 @@ mlp_fwd_kernel(MlpIO io, const h1* __restrict__ weights, int n_samples) {
         n_samples = min(*io.n_dev, n_samples);
         if ((long long)blockIdx.x * WAVES * TILE >= n_samples) return;
     }
-    stage_fwd_weights_once<N_IN, N_HIDDEN, 64 * WAVES>(weights, lds);
+    stage_fwd_weights<N_IN, N_HIDDEN, 64 * WAVES>(weights, lds);
     __syncthreads();
 
     const int lane = threadIdx.x & 63, i = lane & 31, hh = lane >> 5;
@@ -445,8 +403,8 @@ field_fwd_kernel(FieldIO io, const h1* __restrict__ density_w, const h1* __restr
         n_samples = min(*io.n_dev, n_samples);
         if ((long long)blockIdx.x * WAVES * TILE >= n_samples) return;
     }
-    stage_fwd_weights_once<32, 1, 64 * WAVES>(density_w, ldsd);
-    stage_fwd_weights_once<32, 2, 64 * WAVES>(rgb_w, ldsr);
+    stage_fwd_weights<32, 1, 64 * WAVES>(density_w, ldsd);
+    stage_fwd_weights<32, 2, 64 * WAVES>(rgb_w, ldsr);
     __syncthreads();
 
     const int lane = threadIdx.x & 63, i = lane & 31, hh = lane >> 5;
@@ -654,7 +612,7 @@ template <int MT, int NT, int BWD_WAVES, bool SPLIT>
 __device__ __forceinline__ void wgrad_reduce_layer(float* slabs, int n_rows, int n_cols, int wave, int j, int hh,
                                                    const f32x16 (&acc)[MT][NT], float* __restrict__ out, float& nonfinite) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    // SPLIT: one pass per 32-row block of the layer (slabs of 32 x n_cols floats), else the whole layer at once
+    // SPLIT (no caller asks for it today): one pass per 32-row block of the layer (slabs of 32 x n_cols floats), else the whole layer at once
     constexpr int PASSES = SPLIT ? MT : 1, MP = SPLIT ? 1 : MT;
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) {
@@ -777,12 +735,11 @@ struct BwdLds {
     using L = LdsW<N_IN, N_HIDDEN>;
     static constexpr int BWD_WAVES = bwd_waves<N_IN, N_HIDDEN>();
     static constexpr int NXB = (N_IN + 31) / 32;                                   // input blocks
-    static constexpr bool STAGED = bwd_staged<N_IN, N_HIDDEN>();                   // 7 blocks per wave, the first layer's operands reuse the upper layers'
-    static constexpr int NB = STAGED ? 7 : NXB + 4 + (N_HIDDEN == 2 ? 4 : 0) + 1;  // blocks per wave
+    static constexpr int NB = NXB + 4 + (N_HIDDEN == 2 ? 4 : 0) + 1;               // blocks per wave
     static constexpr int W_HALVES = L::SIZE + N_IN * (HID + PAD) + (N_HIDDEN == 2 ? HID * (HID + PAD) : 0) + HID * (16 + PAD);
     static constexpr int OFF_TR = (W_HALVES + 127) / 128 * 128;
     static constexpr int IMG_BYTES = BWD_WAVES * NB * BLK_BYTES;
-    static constexpr int PART_BYTES = BWD_WAVES * (STAGED ? 32 : HID) * (N_IN > HID ? N_IN : HID) * 4;   // one f32 slab per wave of the largest layer (STAGED: of its 32-row halves)
+    static constexpr int PART_BYTES = BWD_WAVES * HID * (N_IN > HID ? N_IN : HID) * 4;   // one f32 slab per wave of the largest layer
     static constexpr int BYTES = OFF_TR * 2 + (IMG_BYTES > PART_BYTES ? IMG_BYTES : PART_BYTES);
 };
 
@@ -856,14 +813,7 @@ mlp_bwd_kernel(MlpBwdIO io, const h1* __restrict__ weights, int n_samples) {
     const int t0 = blockIdx.x * BWD_WAVES + wave;
     const int raw0 = raw_index(t0);                    // in flight while the weights are staged
     int raw_pre = raw_index(t0 + tile_stride);
-    if (NGP_MLP_STAGE_ONCE) {
-        stage_bwd_weights<N_IN, N_HIDDEN, 64 * BWD_WAVES>(weights, lds, OFF_T0, OFF_T1, OFF_TO);
-    } else {
-        stage_fwd_weights<N_IN, N_HIDDEN>(weights, lds);
-        stage_weights(weights, lds + OFF_T0, HID, N_IN, true);
-        if (N_HIDDEN == 2) stage_weights(weights + L::G_W1, lds + OFF_T1, HID, HID, true);
-        stage_weights(weights + L::G_WO, lds + OFF_TO, 16, HID, true);
-    }
+    stage_bwd_weights<N_IN, N_HIDDEN, 64 * BWD_WAVES>(weights, lds, OFF_T0, OFF_T1, OFF_TO);
     fetch(t0, raw0, cur);
     __syncthreads();
     MLP_T(0);                                          // prologue: weights staged, first tile fetched
@@ -1000,39 +950,20 @@ mlp_bwd_kernel(MlpBwdIO io, const h1* __restrict__ weights, int n_samples) {
         }
         MLP_T(2);                                      // dgrad + input-gradient store
         // ---- wgrad (samples on K: through the wave-private LDS image, read back transposed) ----
-        if (!B::STAGED) {
-            wave_lds_sync();                              // the previous tile's reads are behind us (DS ops of a wave run in order)
-            tr_put_nat<N_IN / 16>(img_x, xb, ta);         // N_IN == 16: units 16..31 of the block feed dW columns nobody stores
-            tr_put_dl<4>(img_dh0, dh0b, ta);
-            tr_put_dl<4>(img_h0, h0b, ta);
-            if (N_HIDDEN == 2) {
-                tr_put_dl<4>(img_dh1, dh1b, ta);
-                tr_put_dl<4>(img_h1, h1b, ta);
-            }
-            tr_put_dl<1>(img_dy, dyb, ta);
-            wave_lds_sync();
-            MLP_T(3);                                  // image stores
-            wgrad_tile<2, B::NXB>(img_dh0, img_x, ta, gW0);                               // dW0 (64 x N_IN) = dH0^T X
-            if (N_HIDDEN == 2) wgrad_tile<2, 2>(img_dh1, img_h0, ta, gW1);                // dW1 (64 x 64)   = dH1^T H0
-            wgrad_tile<1, 2>(img_dy, (N_HIDDEN == 2) ? img_h1 : img_h0, ta, gWo);         // dWo (16 x 64)   = dY^T Hlast
-        } else {
-            // 7 blocks: the two upper layers' operands at once, then the first layer's through the blocks they leave behind
-            char* img_b = img;
-            wave_lds_sync();
-            tr_put_dl<1>(img_b, dyb, ta);                                  // block 0 (units 16..31: dW rows nobody stores)
-            tr_put_dl<4>(img_b + 1 * BLK_BYTES, h1b, ta);                  // blocks 1-2
-            tr_put_dl<4>(img_b + 3 * BLK_BYTES, dh1b, ta);                 // blocks 3-4
-            tr_put_dl<4>(img_b + 5 * BLK_BYTES, h0b, ta);                  // blocks 5-6
-            wave_lds_sync();
-            MLP_T(3);
-            wgrad_tile<1, 2>(img_b, img_b + 1 * BLK_BYTES, ta, gWo);
-            wgrad_tile<2, 2>(img_b + 3 * BLK_BYTES, img_b + 5 * BLK_BYTES, ta, gW1);
-            wave_lds_sync();
-            tr_put_dl<4>(img_b, dh0b, ta);                                 // blocks 0-1
-            tr_put_nat<N_IN / 16>(img_b + 2 * BLK_BYTES, xb, ta);          // block 2
-            wave_lds_sync();
-            wgrad_tile<2, B::NXB>(img_b, img_b + 2 * BLK_BYTES, ta, gW0);
+        wave_lds_sync();                                  // the previous tile's reads are behind us (DS ops of a wave run in order)
+        tr_put_nat<N_IN / 16>(img_x, xb, ta);             // N_IN == 16: units 16..31 of the block feed dW columns nobody stores
+        tr_put_dl<4>(img_dh0, dh0b, ta);
+        tr_put_dl<4>(img_h0, h0b, ta);
+        if (N_HIDDEN == 2) {
+            tr_put_dl<4>(img_dh1, dh1b, ta);
+            tr_put_dl<4>(img_h1, h1b, ta);
         }
+        tr_put_dl<1>(img_dy, dyb, ta);
+        wave_lds_sync();
+        MLP_T(3);                                      // image stores
+        wgrad_tile<2, B::NXB>(img_dh0, img_x, ta, gW0);                               // dW0 (64 x N_IN) = dH0^T X
+        if (N_HIDDEN == 2) wgrad_tile<2, 2>(img_dh1, img_h0, ta, gW1);                // dW1 (64 x 64)   = dH1^T H0
+        wgrad_tile<1, 2>(img_dy, (N_HIDDEN == 2) ? img_h1 : img_h0, ta, gWo);         // dWo (16 x 64)   = dY^T Hlast
         MLP_T(4);                                      // wgrad
         cur = nxt;
     }
@@ -1041,9 +972,9 @@ mlp_bwd_kernel(MlpBwdIO io, const h1* __restrict__ weights, int n_samples) {
     constexpr int NT0 = (N_IN / 32 > 0 ? N_IN / 32 : 1);
     float* out = io.wgrad_partial + (size_t)blockIdx.x * L::G_SIZE;
     float nonfinite = 0.f;
-    wgrad_reduce_layer<2, NT0, BWD_WAVES, B::STAGED>(part, HID, N_IN, wave, i, hh, gW0, out, nonfinite);
-    if (N_HIDDEN == 2) wgrad_reduce_layer<2, 2, BWD_WAVES, B::STAGED>(part, HID, HID, wave, i, hh, gW1, out + L::G_W1, nonfinite);
-    wgrad_reduce_layer<1, 2, BWD_WAVES, B::STAGED>(part, 16, HID, wave, i, hh, gWo, out + L::G_WO, nonfinite);
+    wgrad_reduce_layer<2, NT0, BWD_WAVES, false>(part, HID, N_IN, wave, i, hh, gW0, out, nonfinite);
+    if (N_HIDDEN == 2) wgrad_reduce_layer<2, 2, BWD_WAVES, false>(part, HID, HID, wave, i, hh, gW1, out + L::G_W1, nonfinite);
+    wgrad_reduce_layer<1, 2, BWD_WAVES, false>(part, 16, HID, wave, i, hh, gWo, out + L::G_WO, nonfinite);
     // (NaN != 0: taken exactly when a sum was inf / NaN) ... or a feature gradient left the f16 range on its way to the table backward
     // (finite in the f32 accumulator, inf as the half the scatter reads: the dW sums, f32, do not see that one)
     if (io.nonfinite != nullptr && (nonfinite != 0.f || din_max > (io.din_limit > 0.f ? io.din_limit : 65504.f))) atomicOr(io.nonfinite, 1);
@@ -1053,19 +984,16 @@ mlp_bwd_kernel(MlpBwdIO io, const h1* __restrict__ weights, int n_samples) {
 }
 
 // ------------------------------------------------------------------------------------------
-// fused field backward (NGP_FIELD_BWD_FUSED): the colour net's and the density net's backward chained in ONE launch.  What the two
+// fused field backward: the colour net's and the density net's backward chained in ONE launch.  What the two
 // mlp_bwd_kernel launches hand over through memory -- dL/dh (S,16) f16 out and in, h (S,16) in -- stays in registers: the
 // density net's forward is recomputed from the features (bit for bit the h the forward stored), the colour net's input gradient
 // is rounded to f16 exactly as the (S,16) store rounded it and becomes the density net's output gradient in the D order it is
 // produced in.  One prologue (both nets' weights + transposes staged once), one epilogue, one pass over the active list.
 // The twelve dW accumulator tiles of the two nets (192 registers) are pinned in AGPRs: the wgrad MFMAs are issued as inline
 // assembly with "+a" operands, which leaves the 256 VGPRs to forward / dgrad (-amdgpu-mfma-vgpr-form keeps THEIR results in VGPRs).
-// Results: dfeats bit-identical to the two-kernel path; dW partial rows differ in summation order (4 waves of tiles instead of 8
-// for the density net).
+// Results: dfeats bit-identical to the two mlp_bwd_kernel launches (which tests reach through ngp_field_bwd_two_launches); dW partial
+// rows differ in summation order (4 waves of tiles instead of 8 for the density net).
 // ------------------------------------------------------------------------------------------
-#ifndef NGP_FIELD_BWD_FUSED
-#define NGP_FIELD_BWD_FUSED 1          // 0: ngp_field_bwd = the two mlp_bwd_kernel launches (A/B builds; tests reach them through ngp_field_bwd_two_launches)
-#endif
 struct FieldBwdIO {
     const h1* feats;          // [16][S] half2
     const float* dirs;        // (S,3)
@@ -1523,41 +1451,33 @@ int ngp_debug_mlp_timing(unsigned long long* host_out, int reset) {
 int ngp_field_bwd_partials(int n_samples) { return n_samples <= 0 ? 0 : bwd_grid(n_samples); }
 
 // (the colour net's half of ngp_field_bwd: internal)
-static int ngp_rgb_bwd(const ngp_half* h, const float* dirs, const ngp_half* rgb_w, const float* dL_drgbs, float loss_scale, const float* loss_scale_dev,
+static int ngp_rgb_bwd(const ngp_half* h, const float* dirs, const ngp_half* rgb_w, const float* dL_drgbs, float loss_scale,
                 int n_samples, const int32_t* active_idx, const int32_t* n_active, ngp_half* dL_dh, float* wgrad_partial,
-                int32_t* nonfinite, int32_t* nonfinite_clear, ngp_stream_t stream) {
+                ngp_stream_t stream) {
     if (n_samples < 0) return NGP_EINVAL;
     if (n_samples == 0) return 0;
     NGP_CHECK_PTR(h); NGP_CHECK_PTR(dirs); NGP_CHECK_PTR(rgb_w); NGP_CHECK_PTR(dL_drgbs); NGP_CHECK_PTR(dL_dh); NGP_CHECK_PTR(wgrad_partial);
     MlpBwdIO r = {};
     r.fwd.in = (const h1*)h; r.fwd.dirs = dirs; r.fwd.n_out = 3;
-    r.dL_drgbs = dL_drgbs; r.loss_scale = loss_scale; r.loss_scale_dev = loss_scale_dev; r.dL_din = (h1*)dL_dh; r.wgrad_partial = wgrad_partial;
+    r.dL_drgbs = dL_drgbs; r.loss_scale = loss_scale; r.dL_din = (h1*)dL_dh; r.wgrad_partial = wgrad_partial;
     if ((active_idx == nullptr) != (n_active == nullptr)) return NGP_EINVAL;
     r.active = active_idx; r.n_active = n_active;
-    r.nonfinite = nonfinite; r.nonfinite_clear = nonfinite_clear;
     return launch_bwd<32, 2, IN_SH_H, OUT_RGB>(r, (const h1*)rgb_w, n_samples, ngp_stream(stream));
 }
 
-static int density_bwd_guarded(const ngp_half* feats, const ngp_half* density_w, const ngp_half* dL_dh, const float* dL_dsigmas,
-                               float loss_scale, const float* loss_scale_dev, float din_limit, int n_samples, const int32_t* active_idx, const int32_t* n_active,
-                               ngp_half* dfeats, float* wgrad_partial, int32_t* nonfinite, ngp_stream_t stream) {
+int ngp_density_bwd(const ngp_half* feats, const ngp_half* density_w, const ngp_half* dL_dh, const float* dL_dsigmas,
+                    float loss_scale, int n_samples, const int32_t* active_idx, const int32_t* n_active,
+                    ngp_half* dfeats, float* wgrad_partial, ngp_stream_t stream) {
     if (n_samples < 0) return NGP_EINVAL;
     if (n_samples == 0) return 0;
     NGP_CHECK_PTR(feats); NGP_CHECK_PTR(density_w); NGP_CHECK_PTR(dfeats); NGP_CHECK_PTR(wgrad_partial);
     MlpBwdIO d = {};
     d.fwd.in = (const h1*)feats; d.fwd.n_out = 16; d.fwd.out_ld = 16;
     d.dL_dout16 = (const h1*)dL_dh; d.dout_ld = 16;
-    d.dL_dsigmas = dL_dsigmas; d.loss_scale = loss_scale; d.loss_scale_dev = loss_scale_dev; d.din_limit = din_limit; d.dL_din = (h1*)dfeats; d.wgrad_partial = wgrad_partial;
+    d.dL_dsigmas = dL_dsigmas; d.loss_scale = loss_scale; d.dL_din = (h1*)dfeats; d.wgrad_partial = wgrad_partial;
     if ((active_idx == nullptr) != (n_active == nullptr)) return NGP_EINVAL;
     d.active = active_idx; d.n_active = n_active;
-    d.nonfinite = nonfinite;
     return launch_bwd<32, 1, IN_LEVELMAJOR, OUT_DENSITY>(d, (const h1*)density_w, n_samples, ngp_stream(stream));
-}
-
-int ngp_density_bwd(const ngp_half* feats, const ngp_half* density_w, const ngp_half* dL_dh, const float* dL_dsigmas,
-                    float loss_scale, int n_samples, const int32_t* active_idx, const int32_t* n_active,
-                    ngp_half* dfeats, float* wgrad_partial, ngp_stream_t stream) {
-    return density_bwd_guarded(feats, density_w, dL_dh, dL_dsigmas, loss_scale, nullptr, 0.f, n_samples, active_idx, n_active, dfeats, wgrad_partial, nullptr, stream);
 }
 
 int ngp_field_bwd(const ngp_half* feats, const float* dirs, const ngp_half* h, const ngp_half* density_w,
@@ -1568,25 +1488,20 @@ int ngp_field_bwd(const ngp_half* feats, const float* dirs, const ngp_half* h, c
                                  wgrad_partial, nullptr, 0, stream);
 }
 
-// The two-launch form: colour net (writes dL/dh to dh_scratch) then density net (reads it).  nonfinite2 / parity as below.
-static int field_bwd_two_launches(const ngp_half* feats, const float* dirs, const ngp_half* h, const ngp_half* density_w,
-                                  const ngp_half* rgb_w, const float* dL_dsigmas, const float* dL_drgbs, float loss_scale, const float* loss_scale_dev, float din_limit,
-                                  int n_samples, const int32_t* active_idx, const int32_t* n_active,
-                                  ngp_half* dh_scratch, ngp_half* dfeats, float* wgrad_partial, int32_t* nonfinite2, int parity, ngp_stream_t stream) {
-    const int n_part = bwd_grid(n_samples);
-    int32_t* flag = nonfinite2 ? nonfinite2 + (parity & 1) : nullptr;
-    const int rc = ngp_rgb_bwd(h, dirs, rgb_w, dL_drgbs, loss_scale, loss_scale_dev, n_samples, active_idx, n_active, dh_scratch,
-                               wgrad_partial + (size_t)n_part * NGP_DENSITY_NET_PARAMS, flag, nonfinite2 ? nonfinite2 + ((parity & 1) ^ 1) : nullptr, stream);
-    if (rc) return rc;
-    return density_bwd_guarded(feats, density_w, dh_scratch, dL_dsigmas, loss_scale, loss_scale_dev, din_limit, n_samples, active_idx, n_active, dfeats,
-                               wgrad_partial, flag, stream);
-}
-
-// The one-launch form (field_bwd_kernel): h and dL/dh never touch memory.
-static int field_bwd_one_launch(const ngp_half* feats, const float* dirs, const ngp_half* density_w,
-                                const ngp_half* rgb_w, const float* dL_dsigmas, const float* dL_drgbs, float loss_scale, const float* loss_scale_dev, float din_limit,
-                                int n_samples, const int32_t* active_idx, const int32_t* n_active,
-                                ngp_half* dfeats, float* wgrad_partial, int32_t* nonfinite2, int parity, ngp_stream_t stream) {
+// (csrc/ngp_internal.h) the same with the native stepper's overflow guard: nonfinite2 = two device flags; this call ORs 1 into
+// nonfinite2[parity] when a weight-gradient sum of either network is inf / NaN -- or a feature gradient leaves the f16 range -- and
+// clears nonfinite2[parity ^ 1] (the next step's).  loss_scale_dev (may be NULL): a device-side factor on loss_scale, read by the
+// launch (the stepper's dynamic loss scale: GradScaler's scale on top of tiny-cuda-nn's 128).  din_limit: the magnitude beyond which a
+// feature gradient raises the flag (0 = 65504; a data-parallel rank passes 65504 / world: the ranks' gradients are summed in f16).
+// One launch (field_bwd_kernel): h and dL/dh never touch memory, h and dh_scratch are ignored.
+int ngp_field_bwd_guarded(const ngp_half* feats, const float* dirs, const ngp_half* h, const ngp_half* density_w,
+                          const ngp_half* rgb_w, const float* dL_dsigmas, const float* dL_drgbs, float loss_scale, const float* loss_scale_dev, float din_limit,
+                          int n_samples, const int32_t* active_idx, const int32_t* n_active,
+                          ngp_half* dh_scratch, ngp_half* dfeats, float* wgrad_partial, int32_t* nonfinite2, int parity, ngp_stream_t stream) {
+    (void)h; (void)dh_scratch;
+    if (n_samples < 0) return NGP_EINVAL;
+    if (n_samples == 0) return 0;
+    NGP_CHECK_PTR(wgrad_partial);
     NGP_CHECK_PTR(feats); NGP_CHECK_PTR(dirs); NGP_CHECK_PTR(density_w); NGP_CHECK_PTR(rgb_w); NGP_CHECK_PTR(dL_dsigmas);
     NGP_CHECK_PTR(dL_drgbs); NGP_CHECK_PTR(dfeats);
     if ((active_idx == nullptr) != (n_active == nullptr)) return NGP_EINVAL;
@@ -1613,31 +1528,8 @@ static int field_bwd_one_launch(const ngp_half* feats, const float* dirs, const 
     return NGP_LAUNCH_RESULT();
 }
 
-// (csrc/ngp_internal.h) the same with the native stepper's overflow guard: nonfinite2 = two device flags; this call ORs 1 into
-// nonfinite2[parity] when a weight-gradient sum of either network is inf / NaN -- or a feature gradient leaves the f16 range -- and
-// clears nonfinite2[parity ^ 1] (the next step's).  loss_scale_dev (may be NULL): a device-side factor on loss_scale, read by the
-// launch (the stepper's dynamic loss scale: GradScaler's scale on top of tiny-cuda-nn's 128).  din_limit: the magnitude beyond which a
-// feature gradient raises the flag (0 = 65504; a data-parallel rank passes 65504 / world: the ranks' gradients are summed in f16).
-int ngp_field_bwd_guarded(const ngp_half* feats, const float* dirs, const ngp_half* h, const ngp_half* density_w,
-                          const ngp_half* rgb_w, const float* dL_dsigmas, const float* dL_drgbs, float loss_scale, const float* loss_scale_dev, float din_limit,
-                          int n_samples, const int32_t* active_idx, const int32_t* n_active,
-                          ngp_half* dh_scratch, ngp_half* dfeats, float* wgrad_partial, int32_t* nonfinite2, int parity, ngp_stream_t stream) {
-    if (n_samples < 0) return NGP_EINVAL;
-    if (n_samples == 0) return 0;
-    NGP_CHECK_PTR(wgrad_partial);
-    if (NGP_FIELD_BWD_FUSED)
-        return field_bwd_one_launch(feats, dirs, density_w, rgb_w, dL_dsigmas, dL_drgbs, loss_scale, loss_scale_dev, din_limit, n_samples, active_idx, n_active, dfeats,
-                                    wgrad_partial, nonfinite2, parity, stream);
-    return field_bwd_two_launches(feats, dirs, h, density_w, rgb_w, dL_dsigmas, dL_drgbs, loss_scale, loss_scale_dev, din_limit, n_samples, active_idx, n_active, dh_scratch,
-                                  dfeats, wgrad_partial, nonfinite2, parity, stream);
-}
-
-// (csrc/ngp_internal.h) 1 when ngp_field_bwd reads the forward's h_out and writes dh_scratch (the two-launch A/B build), 0 when both
-// may be NULL: callers that own the buffers (the native stepper) skip the forward's h store.
-int ngp_field_bwd_uses_h(void) { return NGP_FIELD_BWD_FUSED ? 0 : 1; }
-
-// (csrc/ngp_internal.h, test hook) ngp_field_bwd as two launches whatever the build's default: the cross-check of the one-launch kernel
-// (dfeats must agree bit for bit; the density net's dW partial rows differ in summation order).
+// (csrc/ngp_internal.h, test hook) ngp_field_bwd as two launches, colour net (writes dL/dh to dh_scratch) then density net (reads it):
+// the cross-check of the one-launch kernel (dfeats must agree bit for bit; the density net's dW partial rows differ in summation order).
 int ngp_field_bwd_two_launches(const ngp_half* feats, const float* dirs, const ngp_half* h, const ngp_half* density_w,
                                const ngp_half* rgb_w, const float* dL_dsigmas, const float* dL_drgbs, float loss_scale,
                                int n_samples, const int32_t* active_idx, const int32_t* n_active,
@@ -1645,8 +1537,10 @@ int ngp_field_bwd_two_launches(const ngp_half* feats, const float* dirs, const n
     if (n_samples < 0) return NGP_EINVAL;
     if (n_samples == 0) return 0;
     NGP_CHECK_PTR(wgrad_partial); NGP_CHECK_PTR(h); NGP_CHECK_PTR(dh_scratch);
-    return field_bwd_two_launches(feats, dirs, h, density_w, rgb_w, dL_dsigmas, dL_drgbs, loss_scale, nullptr, 0.f, n_samples, active_idx, n_active, dh_scratch,
-                                  dfeats, wgrad_partial, nullptr, 0, stream);
+    const int rc = ngp_rgb_bwd(h, dirs, rgb_w, dL_drgbs, loss_scale, n_samples, active_idx, n_active, dh_scratch,
+                               wgrad_partial + (size_t)bwd_grid(n_samples) * NGP_DENSITY_NET_PARAMS, stream);
+    if (rc) return rc;
+    return ngp_density_bwd(feats, density_w, dh_scratch, dL_dsigmas, loss_scale, n_samples, active_idx, n_active, dfeats, wgrad_partial, stream);
 }
 
 int ngp_mlp_fwd(const ngp_half* in, const ngp_half* weights, int n_in, int n_hidden, int n_out, int out_act,

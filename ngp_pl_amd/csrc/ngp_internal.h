@@ -51,10 +51,8 @@ int ngp_adam_use_loss_scaler(float* state, int slot, float growth_factor, float 
  * *found_inf (device i32; NULL when no guarded field backward ran since the last update). */
 struct ngp_stepper;
 int ngp_stepper_before_update(struct ngp_stepper* s, int32_t** found_inf);
-/* 1 when ngp_field_bwd reads h / writes dh_scratch (the two-launch A/B build), 0 when both may be NULL (the one-launch kernel, round 6:
- * h is recomputed from the features and dL/dh handed from the colour net to the density net in registers). */
-int ngp_field_bwd_uses_h(void);
-/* test hook: ngp_field_bwd as the two launches (colour net -> dh_scratch -> density net) whatever the build's default. */
+/* test hook: ngp_field_bwd as two launches (colour net -> dh_scratch -> density net), which read h and write dh_scratch; the one-launch
+ * kernel behind ngp_field_bwd recomputes h from the features and hands dL/dh from the colour net to the density net in registers. */
 int ngp_field_bwd_two_launches(const ngp_half* feats, const float* dirs, const ngp_half* h, const ngp_half* density_w,
                                const ngp_half* rgb_w, const float* dL_dsigmas, const float* dL_drgbs, float loss_scale,
                                int n_samples, const int32_t* active_idx, const int32_t* n_active,

@@ -411,7 +411,7 @@ static int forward_field(ngp_stepper* s, const float* rays_o, const float* rays_
     s->prev_S = S;
     s->two_rounds = two;
     const ngp_half* table = c.enc_half + c.n_density;
-    ngp_half* h_store = ngp_field_bwd_uses_h() ? b.h : nullptr;      // the one-launch field backward recomputes h: the forward need not store it
+    ngp_half* h_store = nullptr;      // the one-launch field backward recomputes h: the forward need not store it
     if (!two) {
         if (!s->expanded[k])
             STEP_TRY(ngp_raymarching_train_write(rays_o, rays_d, b.rays_a[k], b.scratch[k], c.scale, c.exp_step_factor, c.grid_size, c.max_samples, n,

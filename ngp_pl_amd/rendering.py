@@ -226,11 +226,10 @@ class _FusedTrainRender(torch.autograd.Function):
             call("ngp_raymarching_train_write", ptr(rays_o), ptr(rays_d), ptr(rays_a), ptr(scratch), float(model.scale), float(esf),
                  model.grid_size, MAX_SAMPLES, n, ptr(xyzs), ptr(dirs), ptr(deltas), ptr(ts), sq)
             feats = torch.empty(16, S, 2, **f16)
-            h = torch.empty(S, 16, **f16) if _lib.field_bwd_uses_h() else None      # (the one-launch backward recomputes it)
             sigmas = torch.empty(S, **f32); rgbs = torch.empty(S, 3, **f32)
             if S > 0:
                 call("ngp_hashgrid_fwd", ptr(xyzs), ptr(model.xyz_min), ptr(model.xyz_max), ptr(eh[enc.n_mlp:]), C.byref(enc.meta), S, ptr(feats), sq)
-                call("ngp_field_fwd", ptr(feats), ptr(dirs), ptr(eh), ptr(rh), S, ptr(sigmas), ptr(rgbs), ptr(h), sq)
+                call("ngp_field_fwd", ptr(feats), ptr(dirs), ptr(eh), ptr(rh), S, ptr(sigmas), ptr(rgbs), None, sq)       # (the one-launch backward recomputes h)
             total = torch.empty(n, dtype=torch.int64, device=dev)
             opacity = torch.empty(n, **f32); depth = torch.empty(n, **f32); rgb = torch.empty(n, 3, **f32); ws = torch.empty(S, **f32)
             ray_offs = torch.empty(n, **i32); n_active = torch.empty(1, **i32)
@@ -240,7 +239,7 @@ class _FusedTrainRender(torch.autograd.Function):
             rgb_out = torch.empty(n, 3, **f32)
             call("ngp_bg_blend", ptr(rgb), ptr(opacity), ptr(bg), n, ptr(rgb_out), sq)       # rendering.py:161
         ctx.model, ctx.S, ctx.T_threshold = model, S, T_threshold
-        ctx.save_for_backward(rays_a, xyzs, dirs, deltas, ts, feats, h, sigmas, rgbs, ws, opacity, depth, rgb, ray_offs, n_active, bg)
+        ctx.save_for_backward(rays_a, xyzs, dirs, deltas, ts, feats, sigmas, rgbs, ws, opacity, depth, rgb, ray_offs, n_active, bg)
         vr_samples = total.sum()
         rm_samples = torch.tensor(S, dtype=torch.int32)
         ctx.mark_non_differentiable(rays_a, deltas, ts, vr_samples, rm_samples)
@@ -250,7 +249,7 @@ class _FusedTrainRender(torch.autograd.Function):
     def backward(ctx, _g_vr, g_opacity, g_depth, g_rgb, g_ws, _g_rays_a, _g_deltas, _g_ts, _g_rm):
         from . import tcnn
         model, S = ctx.model, ctx.S
-        rays_a, xyzs, dirs, deltas, ts, feats, h, sigmas, rgbs, ws, opacity, depth, rgb, ray_offs, n_active, bg = ctx.saved_tensors
+        rays_a, xyzs, dirs, deltas, ts, feats, sigmas, rgbs, ws, opacity, depth, rgb, ray_offs, n_active, bg = ctx.saved_tensors
         enc, net = model.xyz_encoder, model.rgb_net
         n, dev = rays_a.shape[0], rays_a.device
         none5 = (None,) * 8
@@ -280,10 +279,9 @@ class _FusedTrainRender(torch.autograd.Function):
                  ptr(ray_offs), ptr(active), ptr(xyzs) if nbytes else None, ptr(x_act), sq)
             n_part = call("ngp_field_bwd_partials", S)
             partials = torch.empty(n_part * (enc.n_mlp + net.params.numel()), **f32)
-            dh = torch.empty(S, 16, **f16) if h is not None else None
             dfeats = torch.empty(16, S, 2, **f16)
-            call("ngp_field_bwd", ptr(feats), ptr(dirs), ptr(h), ptr(eh), ptr(rh), ptr(dL_dsigmas), ptr(dL_drgbs), scale, S,
-                 ptr(active), ptr(n_active), ptr(dh), ptr(dfeats), ptr(partials), sq)
+            call("ngp_field_bwd", ptr(feats), ptr(dirs), None, ptr(eh), ptr(rh), ptr(dL_dsigmas), ptr(dL_drgbs), scale, S,
+                 ptr(active), ptr(n_active), None, ptr(dfeats), ptr(partials), sq)
             g16 = model._grid_grad16(dev)
             if nbytes:
                 bin_ws = tcnn.binned_workspace(dev, nbytes)
