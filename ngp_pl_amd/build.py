@@ -38,6 +38,11 @@
                      same way, exactly the brute-force minimum through libngp_meshdist.so's grid; interpolated vertex normals) and
                      the shading of a frame by a rendered normal map behind csrc/meshnormal/ngp_meshnormal.h, which lies beside
                      its sources under csrc/meshnormal/.
+The mesh libraries share source, each header included inside the including library's anonymous namespace: csrc/mesh_host.h (the
+host helpers of the C entry points, every mesh library), csrc/mesh_scan.h (integer sums and prefix sums over a wave, a workgroup
+and an array), csrc/mesh_labels.h (the lanes of a wave grouped by label), csrc/mesh_cells.h (the clustering grid of the simplifier
+and the quadric placement) and csrc/mesh_mix.h (the 64-bit hash of the tables), beside csrc/mesh_compact.h, csrc/mesh_camera.h,
+csrc/mesh_raster.h and csrc/mesh_nearest.h.
 Run as `python -m ngp_pl_amd.build` or through `__graft_entry__.build()`.
 """
 import os
@@ -60,35 +65,35 @@ CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=
 EXTRA = {"mlp.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 MESH_LIB = os.path.join(CSRC, "libngp_mesh.so")
 MESH_SOURCES = [os.path.join("mesh", "mesh.hip")]
-MESH_HEADERS = [os.path.join("mesh", "mc_tables.h"), os.path.join("..", "..", "include", "ngp_mesh.h")]
+MESH_HEADERS = ["mesh_host.h", "mesh_scan.h", os.path.join("mesh", "mc_tables.h"), os.path.join("..", "..", "include", "ngp_mesh.h")]
 # positions and normals are the plain f32 expressions of include/ngp_mesh.h (no fused multiply-add), as tests/mc_reference.py has them
 MESH_CFLAGS = ["-ffp-contract=off"]
 MESHFILTER_LIB = os.path.join(CSRC, "libngp_meshfilter.so")
 MESHFILTER_SOURCES = [os.path.join("meshfilter", "meshfilter.hip")]
-MESHFILTER_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshfilter.h")]
+MESHFILTER_HEADERS = ["mesh_compact.h", "mesh_host.h", "mesh_scan.h", "mesh_labels.h", os.path.join("..", "..", "include", "ngp_meshfilter.h")]
 MESHCULL_LIB = os.path.join(CSRC, "libngp_meshcull.so")
 MESHCULL_SOURCES = [os.path.join("meshcull", "meshcull.hip")]
-MESHCULL_HEADERS = ["mesh_compact.h", "mesh_camera.h", "mesh_raster.h", os.path.join("..", "..", "include", "ngp_meshcull.h")]
+MESHCULL_HEADERS = ["mesh_compact.h", "mesh_host.h", "mesh_scan.h", "mesh_camera.h", "mesh_raster.h", os.path.join("..", "..", "include", "ngp_meshcull.h")]
 # projection, edge functions and depths are the plain f32 expressions of include/ngp_meshcull.h, as tests/mesh_visibility_reference.py has them
 MESHCULL_CFLAGS = ["-ffp-contract=off"]
 MESHSIMPLIFY_LIB = os.path.join(CSRC, "libngp_meshsimplify.so")
 MESHSIMPLIFY_SOURCES = [os.path.join("meshsimplify", "meshsimplify.hip")]
-MESHSIMPLIFY_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshsimplify.h")]
+MESHSIMPLIFY_HEADERS = ["mesh_compact.h", "mesh_host.h", "mesh_scan.h", "mesh_labels.h", "mesh_cells.h", "mesh_mix.h", os.path.join("..", "..", "include", "ngp_meshsimplify.h")]
 # cells, fixed-point fractions and the f64 means are the plain expressions of include/ngp_meshsimplify.h, as tests/mesh_simplify_reference.py has them
 MESHSIMPLIFY_CFLAGS = ["-ffp-contract=off"]
 MESHTSDF_LIB = os.path.join(CSRC, "libngp_meshtsdf.so")
 MESHTSDF_SOURCES = [os.path.join("meshtsdf", "meshtsdf.hip")]
-MESHTSDF_HEADERS = ["mesh_camera.h", os.path.join("..", "..", "include", "ngp_meshtsdf.h")]
+MESHTSDF_HEADERS = ["mesh_host.h", "mesh_camera.h", os.path.join("..", "..", "include", "ngp_meshtsdf.h")]
 # lattice points, projection and truncated distances are the plain f32 expressions of include/ngp_meshtsdf.h, as tests/mesh_tsdf_reference.py has them
 MESHTSDF_CFLAGS = ["-ffp-contract=off"]
 MESHSMOOTH_LIB = os.path.join(CSRC, "libngp_meshsmooth.so")
 MESHSMOOTH_SOURCES = [os.path.join("meshsmooth", "meshsmooth.hip")]
-MESHSMOOTH_HEADERS = [os.path.join("..", "..", "include", "ngp_meshsmooth.h")]
+MESHSMOOTH_HEADERS = ["mesh_host.h", "mesh_scan.h", "mesh_mix.h", os.path.join("..", "..", "include", "ngp_meshsmooth.h")]
 # grid states, the f64 steps and the normals are the plain expressions of include/ngp_meshsmooth.h, as tests/mesh_smooth_reference.py has them
 MESHSMOOTH_CFLAGS = ["-ffp-contract=off"]
 MESHTEX_LIB = os.path.join(CSRC, "libngp_meshtex.so")
 MESHTEX_SOURCES = [os.path.join("meshtex", "meshtex.hip")]
-MESHTEX_HEADERS = ["mesh_camera.h", "mesh_raster.h", os.path.join("..", "..", "include", "ngp_meshtex.h")]
+MESHTEX_HEADERS = ["mesh_host.h", "mesh_camera.h", "mesh_raster.h", os.path.join("..", "..", "include", "ngp_meshtex.h")]
 # texel points, directions, projection, barycentric weights and the bilinear lookup are the plain f32 expressions of include/ngp_meshtex.h, as tests/mesh_texture_reference.py has them
 MESHTEX_CFLAGS = ["-ffp-contract=off"]
 METRICS_LIB = os.path.join(CSRC, "libngp_metrics.so")
@@ -98,32 +103,32 @@ METRICS_HEADERS = [os.path.join("..", "..", "include", "ngp_metrics.h")]
 METRICS_CFLAGS = ["-ffp-contract=off"]
 MESHDIST_LIB = os.path.join(CSRC, "libngp_meshdist.so")
 MESHDIST_SOURCES = [os.path.join("meshdist", "meshdist.hip")]
-MESHDIST_HEADERS = ["mesh_nearest.h", os.path.join("..", "..", "include", "ngp_meshdist.h")]
+MESHDIST_HEADERS = ["mesh_host.h", "mesh_scan.h", "mesh_nearest.h", os.path.join("..", "..", "include", "ngp_meshdist.h")]
 # samples, the closest point of a triangle and the squared distance are the plain f32 expressions of include/ngp_meshdist.h, as tests/mesh_distance_reference.py has them
 MESHDIST_CFLAGS = ["-ffp-contract=off"]
 MESHQUADRIC_LIB = os.path.join(CSRC, "libngp_meshquadric.so")
 MESHQUADRIC_SOURCES = [os.path.join("meshquadric", "meshquadric.hip")]
-MESHQUADRIC_HEADERS = [os.path.join("..", "..", "include", "ngp_meshquadric.h")]
+MESHQUADRIC_HEADERS = ["mesh_host.h", "mesh_scan.h", "mesh_labels.h", "mesh_cells.h", os.path.join("..", "..", "include", "ngp_meshquadric.h")]
 # cells, planes, weights, the rounding to int64 and the f64 solve are the plain expressions of include/ngp_meshquadric.h, as tests/mesh_quadric_reference.py has them
 MESHQUADRIC_CFLAGS = ["-ffp-contract=off"]
 MESHDECIMATE_LIB = os.path.join(CSRC, "libngp_meshdecimate.so")
 MESHDECIMATE_SOURCES = [os.path.join("meshdecimate", "meshdecimate.hip")]
-MESHDECIMATE_HEADERS = ["mesh_compact.h", os.path.join("..", "..", "include", "ngp_meshdecimate.h")]
+MESHDECIMATE_HEADERS = ["mesh_compact.h", "mesh_host.h", "mesh_scan.h", os.path.join("..", "..", "include", "ngp_meshdecimate.h")]
 # cross products, the flip and error tests and the rounding of the costs to int64 are the plain f64 expressions of include/ngp_meshdecimate.h, as tests/mesh_decimate_reference.py has them
 MESHDECIMATE_CFLAGS = ["-ffp-contract=off"]
 MESHATLAS_LIB = os.path.join(CSRC, "libngp_meshatlas.so")
 MESHATLAS_SOURCES = [os.path.join("meshatlas", "meshatlas.hip")]
-MESHATLAS_HEADERS = ["mesh_camera.h", "mesh_raster.h", os.path.join("meshatlas", "ngp_meshatlas.h")]
+MESHATLAS_HEADERS = ["mesh_host.h", "mesh_scan.h", "mesh_camera.h", "mesh_raster.h", os.path.join("meshatlas", "ngp_meshatlas.h")]
 # edge lengths, class thresholds, texel points, projection, barycentric weights and the bilinear lookup are the plain f32 expressions of csrc/meshatlas/ngp_meshatlas.h, as tests/mesh_atlas_reference.py has them
 MESHATLAS_CFLAGS = ["-ffp-contract=off"]
 MESHPHOTO_LIB = os.path.join(CSRC, "libngp_meshphoto.so")
 MESHPHOTO_SOURCES = [os.path.join("meshphoto", "meshphoto.hip")]
-MESHPHOTO_HEADERS = ["mesh_camera.h", os.path.join("meshphoto", "ngp_meshphoto.h")]
+MESHPHOTO_HEADERS = ["mesh_host.h", "mesh_camera.h", os.path.join("meshphoto", "ngp_meshphoto.h")]
 # projection, the viewing angle, the depth test, the bilinear sample and the weighted sums are the plain f32 expressions of csrc/meshphoto/ngp_meshphoto.h, as tests/mesh_photo_reference.py has them
 MESHPHOTO_CFLAGS = ["-ffp-contract=off"]
 MESHNORMAL_LIB = os.path.join(CSRC, "libngp_meshnormal.so")
 MESHNORMAL_SOURCES = [os.path.join("meshnormal", "meshnormal.hip")]
-MESHNORMAL_HEADERS = ["mesh_nearest.h", os.path.join("meshnormal", "ngp_meshnormal.h")]
+MESHNORMAL_HEADERS = ["mesh_host.h", "mesh_nearest.h", os.path.join("meshnormal", "ngp_meshnormal.h")]
 # the orientation test, the closest point of a triangle, the interpolated normal and the shading are the plain f32 expressions of csrc/meshnormal/ngp_meshnormal.h, as tests/mesh_normal_reference.py has them
 MESHNORMAL_CFLAGS = ["-ffp-contract=off"]
 

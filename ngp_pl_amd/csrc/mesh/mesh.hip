@@ -20,14 +20,14 @@
 #define NGP_MC_STORAGE static __constant__ const
 #include "mc_tables.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
+
+#include "../mesh_host.h"
+#include "../mesh_scan.h"
 
 constexpr int MC_THREADS = 256;
 constexpr int MC_ITERS = 8;
 constexpr int BRICK = MC_THREADS * MC_ITERS;
-constexpr int SCAN_THREADS = 1024;
 constexpr int MAX_AXIS = 65535;
 constexpr long long MAX_POINTS = 1LL << 36;
 static_assert(3 * BRICK < (1 << 16) && NGP_MC_MAX_TRIS * BRICK < (1 << 15), "packed brick counts overflow");
@@ -47,29 +47,6 @@ __device__ inline void decode(long long p, const Dims& d, int& i, int& j, int& k
     unsigned long long kk = row / (unsigned)d.ny;
     k = (int)kk;
     j = (int)(row - kk * d.ny);
-}
-
-// exclusive prefix of v over the 256 threads of the block, and the block total
-__device__ inline int block_exscan(int v, int& total, int* lds4) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds4[w] = x;
-    __syncthreads();
-    int pre = 0;
-    total = 0;
-#pragma unroll
-    for (int q = 0; q < MC_THREADS / 64; ++q) {
-        int s = lds4[q];
-        pre += q < w ? s : 0;
-        total += s;
-    }
-    __syncthreads();
-    return pre + x - v;
 }
 
 __global__ __launch_bounds__(MC_THREADS) void mc_count(const float* __restrict__ vol, Dims d, float thr,
@@ -97,15 +74,14 @@ __global__ __launch_bounds__(MC_THREADS) void mc_count(const float* __restrict__
         flags[p] = (uint8_t)(in0 | mask << 1);
         acc += __popc(mask) | tris << 16;
     }
-    // block sum of the packed counts (fits: static_assert above)
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) brick_counts[blockIdx.x] = lds4[0] + lds4[1] + lds4[2] + lds4[3];
+    const int total = block_sum<MC_THREADS>(acc, lds4);    // of the packed counts (fits: static_assert above)
+    if (threadIdx.x == 0) brick_counts[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(SCAN_THREADS) void mc_scan_bricks(const int* __restrict__ brick_counts, int nb,
                                                                long long* __restrict__ brick_offsets, long long* __restrict__ totals) {
+    // scan_array of ../mesh_scan.h restated for the two packed fields at once, on purpose: two calls of it, one per half-word,
+    // read the 64 counts a thread has at 512^3 four times instead of twice and cost marching cubes 0.1 ms there
     __shared__ long long sv[2][SCAN_THREADS], st[2][SCAN_THREADS];
     const int t = threadIdx.x;
     const int per = (nb + SCAN_THREADS - 1) / SCAN_THREADS;
@@ -170,7 +146,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_emit_vertices(const float* __re
         const bool live = p < d.n;                      // block-uniform loop: every thread takes part in the scan
         const int mask = live ? flags[p] >> 1 : 0;
         int total;
-        const long long v0 = carry + block_exscan(__popc(mask), total, lds4);
+        const long long v0 = carry + block_exscan<MC_THREADS, int>(__popc(mask), total, lds4);
         carry += total;
         if (!live) continue;
         voff[p] = (int)v0;                              // fits: the caller's total is <= INT32_MAX (ngp_mesh_emit)
@@ -236,7 +212,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_emit_faces(Dims d, const uint8_
         }
         const int nt = NGP_MC_TRI_COUNT[cube];
         int total;
-        const long long f0 = carry + block_exscan(nt, total, lds4);
+        const long long f0 = carry + block_exscan<MC_THREADS>(nt, total, lds4);
         carry += total;
         for (int tr = 0; tr < nt; ++tr) {
             if (f0 + tr >= cap) break;
@@ -258,8 +234,6 @@ __global__ __launch_bounds__(MC_THREADS) void mc_lattice_points(Dims d, Geom g, 
     decode(begin + s, d, idx[0], idx[1], idx[2]);
     for (int a = 0; a < 3; ++a) xyz[3 * s + a] = g.lo[a] + (float)idx[a] * g.h[a];
 }
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 bool dims_ok(int nx, int ny, int nz, Dims& d) {
     if (nx < 2 || ny < 2 || nz < 2 || nx > MAX_AXIS || ny > MAX_AXIS || nz > MAX_AXIS) return false;
@@ -297,8 +271,6 @@ bool geom_ok(const Dims& d, const float* b6, Geom& g) {
     }
     return true;
 }
-
-int launched() { return (int)hipGetLastError(); }
 
 }  // namespace
 

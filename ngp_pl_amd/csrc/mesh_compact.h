@@ -1,5 +1,6 @@
-// Order-preserving compaction of an indexed triangle mesh, shared by libngp_meshfilter.so and libngp_meshcull.so: each includes
-// this header inside its own anonymous namespace and supplies the rule that keeps a face as a functor
+// Order-preserving compaction of an indexed triangle mesh, shared by libngp_meshfilter.so, libngp_meshcull.so,
+// libngp_meshsimplify.so and libngp_meshdecimate.so: each includes this header inside its own anonymous namespace (the sums and
+// scans of mesh_scan.h and the host helpers of mesh_host.h come with it) and supplies the rule that keeps a face as a functor
 //     struct Keep { __device__ bool operator()(const int v[3]) const; };      // v: the face's indices, all inside [0, n_v)
 // A face with an index outside [0, n_v) is never kept and nothing is read through it.  A vertex is kept when a kept face references it.
 // Blocks of BLOCK_ITEMS consecutive faces / vertices, so that a block's output is one contiguous range:
@@ -12,10 +13,12 @@
 #ifndef NGP_MESH_COMPACT_H
 #define NGP_MESH_COMPACT_H
 
+#include "mesh_host.h"
+#include "mesh_scan.h"
+
 constexpr int THREADS = 256;
 constexpr int ITERS = 8;
 constexpr int BLOCK_ITEMS = THREADS * ITERS;
-constexpr int SCAN_THREADS = 1024;
 
 // reads face f; false if an index is outside [0, n_v)
 __device__ inline bool load_face(const int* __restrict__ faces, long long f, unsigned n_v, int v[3]) {
@@ -23,40 +26,6 @@ __device__ inline bool load_face(const int* __restrict__ faces, long long f, uns
     v[1] = faces[3 * f + 1];
     v[2] = faces[3 * f + 2];
     return (unsigned)v[0] < n_v && (unsigned)v[1] < n_v && (unsigned)v[2] < n_v;
-}
-
-// block sum over THREADS threads
-__device__ inline int block_sum(int acc, int* lds4) {
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for (int q = 0; q < THREADS / 64; ++q) total += lds4[q];
-    return total;
-}
-
-// exclusive prefix of v over the THREADS threads of the block, and the block total
-__device__ inline int block_exscan(int v, int& total, int* lds4) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds4[w] = x;
-    __syncthreads();
-    int pre = 0;
-    total = 0;
-#pragma unroll
-    for (int q = 0; q < THREADS / 64; ++q) {
-        int s = lds4[q];
-        pre += q < w ? s : 0;
-        total += s;
-    }
-    __syncthreads();
-    return pre + x - v;
 }
 
 template <class Keep>
@@ -79,7 +48,7 @@ __global__ __launch_bounds__(THREADS) void mf_mark_faces(Keep keep, const int* _
         used[v[2]] = 1;
         ++acc;
     }
-    const int total = block_sum(acc, lds4);
+    const int total = block_sum<THREADS>(acc, lds4);
     if (threadIdx.x == 0) face_counts[blockIdx.x] = total;
 }
 
@@ -91,43 +60,16 @@ __global__ __launch_bounds__(THREADS) void mf_count_vertices(const uint8_t* __re
         const long long v = base + r * THREADS + threadIdx.x;
         if (v < n_v) acc += used[v] != 0;
     }
-    const int total = block_sum(acc, lds4);
+    const int total = block_sum<THREADS>(acc, lds4);
     if (threadIdx.x == 0) vertex_counts[blockIdx.x] = total;
-}
-
-// exclusive int64 scan of counts[0..nb) into offsets by the whole workgroup; returns the total
-__device__ inline long long scan_array(const int* __restrict__ counts, int nb, long long* __restrict__ offsets, long long (*s)[SCAN_THREADS]) {
-    const int t = threadIdx.x;
-    const int per = (nb + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int b0 = min(nb, t * per), b1 = min(nb, b0 + per);
-    long long mine = 0;
-    for (int b = b0; b < b1; ++b) mine += counts[b];
-    int cur = 0;
-    s[0][t] = mine;
-    __syncthreads();
-    for (int o = 1; o < SCAN_THREADS; o <<= 1) {        // inclusive Hillis-Steele over the per-thread sums
-        long long a = s[cur][t];
-        if (t >= o) a += s[cur][t - o];
-        s[cur ^ 1][t] = a;
-        cur ^= 1;
-        __syncthreads();
-    }
-    long long off = s[cur][t] - mine;
-    for (int b = b0; b < b1; ++b) {
-        offsets[b] = off;
-        off += counts[b];
-    }
-    const long long total = s[cur][SCAN_THREADS - 1];
-    __syncthreads();
-    return total;
 }
 
 __global__ __launch_bounds__(SCAN_THREADS) void mf_scan_blocks(const int* __restrict__ vertex_counts, int nbv, long long* __restrict__ vertex_offsets,
                                                                const int* __restrict__ face_counts, int nbf, long long* __restrict__ face_offsets,
                                                                long long* __restrict__ totals) {
     __shared__ long long s[2][SCAN_THREADS];
-    const long long tv = scan_array(vertex_counts, nbv, vertex_offsets, s);
-    const long long tf = scan_array(face_counts, nbf, face_offsets, s);
+    const long long tv = scan_array([=](long long b) { return (long long)vertex_counts[b]; }, nbv, vertex_offsets, s);
+    const long long tf = scan_array([=](long long b) { return (long long)face_counts[b]; }, nbf, face_offsets, s);
     if (threadIdx.x == 0) {
         totals[0] = tv;
         totals[1] = tf;
@@ -154,7 +96,7 @@ __global__ __launch_bounds__(THREADS) void mf_emit_vertices(const uint8_t* __res
         const long long v = base + r * THREADS + threadIdx.x;
         const int k = v < n_v && used[v] != 0;         // block-uniform loop: every thread takes part in the scan
         int total;
-        const long long nv = carry + block_exscan(k, total, lds4);
+        const long long nv = carry + block_exscan<THREADS>(k, total, lds4);
         carry += total;
         if (!k || nv >= cap) continue;
         remap[v] = (int)nv;                             // fits: the caller's total is <= n_vertices <= INT32_MAX
@@ -176,7 +118,7 @@ __global__ __launch_bounds__(THREADS) void mf_emit_faces(Keep keep, const int* _
         int v[3];
         const int k = face_kept(keep, faces, f, n_v, n_f, v);
         int total;
-        const long long nf = carry + block_exscan(k, total, lds4);
+        const long long nf = carry + block_exscan<THREADS>(k, total, lds4);
         carry += total;
         if (!k || nf >= cap) continue;
         faces_out[3 * nf] = remap[v[0]];
@@ -184,12 +126,6 @@ __global__ __launch_bounds__(THREADS) void mf_emit_faces(Keep keep, const int* _
         faces_out[3 * nf + 2] = remap[v[2]];
     }
 }
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-inline bool sizes_ok(int64_t n_v, int64_t n_f) { return n_v >= 0 && n_f >= 0 && n_v <= INT32_MAX && n_f <= INT32_MAX; }
-
-inline long long blocks_of(long long n, int per) { return (n + per - 1) / per; }
 
 struct Layout {
     size_t used, remap, vcounts, fcounts, voffsets, foffsets, total;
@@ -210,8 +146,6 @@ inline Layout layout(long long n_v, long long n_f) {
     l.total = l.foffsets + (size_t)l.nbf * 8;
     return l;
 }
-
-inline int launched() { return (int)hipGetLastError(); }
 
 // Pass 1 on stream s: marks, block counts, the device scan; totals = {kept vertices, kept faces}.  The caller has checked the
 // arguments: sizes in range and not both 0, workspace of layout(n_v, n_f).total bytes.

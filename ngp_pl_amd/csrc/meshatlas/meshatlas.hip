@@ -26,15 +26,15 @@
 
 #include "ngp_meshatlas.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
+
+#include "../mesh_host.h"
+#include "../mesh_scan.h"
 
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
 constexpr int ITERS = 8;
 constexpr int BLOCK_FACES = THREADS * ITERS;            // 2048
-constexpr int SCAN_THREADS = 1024;
 constexpr int NC = NGP_MESHATLAS_CLASSES;
 constexpr int MAX_WH = 16384;
 constexpr float INF = __builtin_inff();
@@ -42,12 +42,6 @@ constexpr unsigned long long NO_KEY = ~0ull;
 
 // T_c: 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256
 __host__ __device__ inline int ladder(int c) { return c < 4 ? c + 1 : ((c & 1) ? 8 << ((c - 4) >> 1) : 3 << (((c - 4) >> 1) + 1)); }
-
-inline long long blocks_of(long long n, int per) { return (n + per - 1) / per; }
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-inline int launched() { return (int)hipGetLastError(); }
 
 inline bool finite3(const float* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 
@@ -201,33 +195,11 @@ __global__ __launch_bounds__(THREADS) void atlas_count(const float* __restrict__
 // exclusive int64 scan of hist[0..n) into offsets by one workgroup, and the 16 class totals
 __global__ __launch_bounds__(SCAN_THREADS) void atlas_scan(const int* __restrict__ hist, int nb, long long* __restrict__ offsets,
                                                            long long* __restrict__ counts) {
-    __shared__ long long sm[2][SCAN_THREADS];
-    __shared__ long long s_start[NC + 1];
+    __shared__ long long s[2][SCAN_THREADS];
     const int t = threadIdx.x;
-    const long long n = (long long)NC * nb;
-    const long long per = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-    const long long b0 = min(n, t * per), b1 = min(n, b0 + per);
-    long long mine = 0;
-    for (long long b = b0; b < b1; ++b) mine += hist[b];
-    int cur = 0;
-    sm[0][t] = mine;
-    __syncthreads();
-    for (int o = 1; o < SCAN_THREADS; o <<= 1) {        // inclusive Hillis-Steele over the per-thread sums
-        long long a = sm[cur][t];
-        if (t >= o) a += sm[cur][t - o];
-        sm[cur ^ 1][t] = a;
-        cur ^= 1;
-        __syncthreads();
-    }
-    long long off = sm[cur][t] - mine;
-    for (long long b = b0; b < b1; ++b) {
-        offsets[b] = off;
-        if (b % nb == 0) s_start[b / nb] = off;         // where class 15 - b / nb begins
-        off += hist[b];
-    }
-    if (t == 0) s_start[NC] = sm[cur][SCAN_THREADS - 1];
-    __syncthreads();
-    if (t < NC) counts[NC - 1 - t] = s_start[t + 1] - s_start[t];
+    const long long total = scan_array([=](long long b) { return (long long)hist[b]; }, (long long)NC * nb, offsets, s);
+    // scan_array closed with a barrier: class 15 - t begins at offsets[t * nb] and ends where the next one begins
+    if (t < NC) counts[NC - 1 - t] = (t + 1 < NC ? offsets[(size_t)(t + 1) * nb] : total) - offsets[(size_t)t * nb];
 }
 
 __global__ __launch_bounds__(THREADS) void atlas_scatter(const uint8_t* __restrict__ face_class, long long n_f,

@@ -16,8 +16,6 @@
 
 #include "../../../include/ngp_meshcull.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
 
 #include "../mesh_compact.h"                           // THREADS and load_face, which mesh_raster.h expects

@@ -24,8 +24,6 @@
 
 #include "../../../include/ngp_meshdecimate.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
 
 #include "../mesh_compact.h"
@@ -109,12 +107,6 @@ __device__ inline bool finite3(float x, float y, float z) {
     return fabsf(x) < inf && fabsf(y) < inf && fabsf(z) < inf;         // false for NaN
 }
 
-__device__ inline long long wave_sum(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 __global__ __launch_bounds__(THREADS) void md_init(const int* __restrict__ faces, long long n_v, long long n_f, int* __restrict__ cur) {
     const long long f = (long long)blockIdx.x * THREADS + threadIdx.x;
     if (f >= n_f) return;
@@ -141,12 +133,7 @@ __global__ __launch_bounds__(THREADS) void md_alloc(const int* __restrict__ degr
     const long long v = (long long)blockIdx.x * THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int d = v < n_v ? degree[v] : 0;
-    int x = d;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
+    const int x = wave_incscan(d);
     const int total = __shfl(x, 63, 64);
     unsigned base = 0;
     if (lane == 63 && total) base = atomicAdd(&counters->cursor, (unsigned)total);

@@ -4,7 +4,8 @@
 //
 //   face_counts     one thread per face: k * k (rule 1), 0 for a face that is not usable.
 //   block_sums / scan_block_sums / offsets   the integer exclusive scan shared by the sampler (int64 offsets per face) and the grid
-//                   (uint32 list starts per cell): 256 threads x 8 elements per workgroup, the workgroup sums scanned by one workgroup.
+//                   (uint32 list starts per cell): 256 threads x 8 elements per workgroup, the workgroup sums scanned by one workgroup
+//                   (the sums and scans of ../mesh_scan.h).
 //   emit_samples    one thread per sample: a binary search of the face offsets, then rule 1.  Writes are coalesced whatever k is.
 //   bin_faces<FILL> one thread per face over the cells of its padded index box: an integer atomic per cell, the count in pass 1 and
 //                   the slot in pass 2.
@@ -19,9 +20,10 @@
 
 #include "../../../include/ngp_meshdist.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
+
+#include "../mesh_host.h"
+#include "../mesh_scan.h"
 
 constexpr int THREADS = 256;
 constexpr int SCAN_ITEMS = NGP_MESHDIST_SCAN_BLOCK / THREADS;        // 8
@@ -71,64 +73,34 @@ __global__ __launch_bounds__(THREADS) void face_counts(const float* __restrict__
 // ---- the scan: counts (n) -> exclusive offsets (n + 1), the last one the total
 
 __global__ __launch_bounds__(THREADS) void block_sums(const int32_t* __restrict__ counts, long long n, long long* __restrict__ bsum) {
-    __shared__ long long part[THREADS];
+    __shared__ long long lds4[THREADS / 64];
     const long long base = (long long)blockIdx.x * NGP_MESHDIST_SCAN_BLOCK + (long long)threadIdx.x * SCAN_ITEMS;
     long long s = 0;
 #pragma unroll
     for (int j = 0; j < SCAN_ITEMS; ++j)
         if (base + j < n) s += (uint32_t)counts[base + j];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = THREADS / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsum[blockIdx.x] = part[0];
+    const long long total = block_sum<THREADS>(s, lds4);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
 // one workgroup: bsum becomes its own exclusive scan, *total the sum
-__global__ __launch_bounds__(THREADS) void scan_block_sums(long long* __restrict__ bsum, long long nb, long long* __restrict__ total) {
-    __shared__ long long part[THREADS];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (long long base = 0; base < nb; base += THREADS) {
-        const long long i = base + threadIdx.x;
-        const long long own = i < nb ? bsum[i] : 0;
-        part[threadIdx.x] = own;
-        __syncthreads();
-        for (int off = 1; off < THREADS; off <<= 1) {       // inclusive scan
-            const long long add = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < nb) bsum[i] = carry + part[threadIdx.x] - own;
-        __syncthreads();
-        if (threadIdx.x == THREADS - 1) carry += part[THREADS - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
+__global__ __launch_bounds__(SCAN_THREADS) void scan_block_sums(long long* bsum, long long nb, long long* __restrict__ total) {
+    __shared__ long long s[2][SCAN_THREADS];
+    const long long sum = scan_array([=](long long b) { return bsum[b]; }, nb, bsum, s);
+    if (threadIdx.x == 0) *total = sum;
 }
 
 template <typename T>
 __global__ __launch_bounds__(THREADS) void offsets(const int32_t* __restrict__ counts, long long n, const long long* __restrict__ bsum,
                                                    T* __restrict__ out) {
-    __shared__ long long part[THREADS];
+    __shared__ long long lds4[THREADS / 64];
     const long long base = (long long)blockIdx.x * NGP_MESHDIST_SCAN_BLOCK + (long long)threadIdx.x * SCAN_ITEMS;
     long long own = 0;
 #pragma unroll
     for (int j = 0; j < SCAN_ITEMS; ++j)
         if (base + j < n) own += (uint32_t)counts[base + j];
-    part[threadIdx.x] = own;
-    __syncthreads();
-    for (int off = 1; off < THREADS; off <<= 1) {
-        const long long add = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    long long at = bsum[blockIdx.x] + part[threadIdx.x] - own;
+    long long total;
+    long long at = bsum[blockIdx.x] + block_exscan<THREADS>(own, total, lds4);
 #pragma unroll
     for (int j = 0; j < SCAN_ITEMS; ++j) {
         if (base + j < n) {
@@ -331,8 +303,6 @@ __global__ __launch_bounds__(64) void stats_finish(const double* __restrict__ pa
 
 // ---- host side
 
-inline int launched() { return (int)hipGetLastError(); }
-
 inline long long scan_blocks(long long n) { return (n + NGP_MESHDIST_SCAN_BLOCK - 1) / NGP_MESHDIST_SCAN_BLOCK; }
 inline size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
 
@@ -419,7 +389,7 @@ NGP_API int ngp_meshdist_sample_count(const float* vertices, const int32_t* face
     hipLaunchKernelGGL(face_counts, dim3((unsigned)((n_faces + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, vertices, faces, (int)n_vertices,
                        (int)n_faces, spacing, w.counts);
     hipLaunchKernelGGL(block_sums, dim3((unsigned)nb), dim3(THREADS), 0, s, (const int32_t*)w.counts, (long long)n_faces, w.bsum);
-    hipLaunchKernelGGL(scan_block_sums, dim3(1), dim3(THREADS), 0, s, w.bsum, nb, (long long*)total);
+    hipLaunchKernelGGL(scan_block_sums, dim3(1), dim3(SCAN_THREADS), 0, s, w.bsum, nb, (long long*)total);
     hipLaunchKernelGGL(offsets<long long>, dim3((unsigned)nb), dim3(THREADS), 0, s, (const int32_t*)w.counts, (long long)n_faces,
                        (const long long*)w.bsum, w.start);
     return launched();
@@ -461,7 +431,7 @@ NGP_API int ngp_meshdist_grid_count(const float* vertices, const int32_t* faces,
         hipLaunchKernelGGL(bin_faces<false>, dim3((unsigned)((n_faces + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, vertices, faces,
                            (int)n_vertices, (int)n_faces, g, w.counts, (const uint32_t*)nullptr, (int32_t*)nullptr, 0);
     hipLaunchKernelGGL(block_sums, dim3((unsigned)nb), dim3(THREADS), 0, s, (const int32_t*)w.counts, cells, w.bsum);
-    hipLaunchKernelGGL(scan_block_sums, dim3(1), dim3(THREADS), 0, s, w.bsum, nb, (long long*)total);
+    hipLaunchKernelGGL(scan_block_sums, dim3(1), dim3(SCAN_THREADS), 0, s, w.bsum, nb, (long long*)total);
     hipLaunchKernelGGL(offsets<uint32_t>, dim3((unsigned)nb), dim3(THREADS), 0, s, (const int32_t*)w.counts, cells, (const long long*)w.bsum,
                        w.start);
     return launched();

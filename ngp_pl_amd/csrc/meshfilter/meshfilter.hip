@@ -18,11 +18,10 @@
 
 #include "../../../include/ngp_meshfilter.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
 
 #include "../mesh_compact.h"
+#include "../mesh_labels.h"
 
 __device__ inline int ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -85,16 +84,10 @@ __global__ __launch_bounds__(THREADS) void uf_face_labels(const int* __restrict_
         if (load_face(faces, f, (unsigned)n_v, v)) l = label[v[0]];
         face_label[f] = l;
     }
-    // wave-uniform loop over the distinct labels present: one atomic per label and wave
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(l >= 0);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int cur = __shfl(l, leader, 64);
-        const unsigned long long same = __ballot(l == cur);
-        if (lane == leader && atomicAdd(component_faces + cur, __popcll(same)) == 0) atomicAdd(n_components, 1ull);
-        todo &= ~same;
-    }
+    // one atomic per distinct label and wave
+    for_each_label(l, [&](int cur, unsigned long long same, int first) {
+        if ((int)(threadIdx.x & 63) == first && atomicAdd(component_faces + cur, __popcll(same)) == 0) atomicAdd(n_components, 1ull);
+    });
 }
 
 // the filter's rule: the label of the face's first vertex is kept

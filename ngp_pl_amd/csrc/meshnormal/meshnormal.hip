@@ -15,9 +15,9 @@
 
 #include "ngp_meshnormal.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
+
+#include "../mesh_host.h"
 
 constexpr int THREADS = 256;
 constexpr float SLACK_FACTOR = (float)NGP_MESHNORMAL_SLACK_ULPS * 0x1p-23f;
@@ -121,8 +121,6 @@ __global__ __launch_bounds__(THREADS) void shade(const float* __restrict__ albed
 }
 
 // ---- host side
-
-inline int launched() { return (int)hipGetLastError(); }
 
 inline long long scan_blocks(long long n) { return (n + NGP_MESHNORMAL_SCAN_BLOCK - 1) / NGP_MESHNORMAL_SCAN_BLOCK; }
 

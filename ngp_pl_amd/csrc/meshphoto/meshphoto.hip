@@ -18,9 +18,9 @@
 
 #include "ngp_meshphoto.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
+
+#include "../mesh_host.h"
 
 constexpr int THREADS = 256;
 constexpr int CAM_TILE = 64;                            // cameras per LDS tile: CAM_FLOATS floats each (4 KiB)
@@ -166,8 +166,6 @@ __global__ __launch_bounds__(THREADS) void photo_resolve(const float* __restrict
 }
 
 inline bool host_finite(float x) { return x - x == 0.f; }
-
-inline int launched() { return (int)hipGetLastError(); }
 
 }  // namespace
 

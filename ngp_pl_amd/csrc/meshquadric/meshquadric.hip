@@ -7,9 +7,10 @@
 //   mq_members       one thread per vertex: n and P of the vertex go to its label's sums;
 //   mq_corners       one thread per corner (3 per face): the corner's plane, weighted by the face's area in cells, goes to the ten
 //                    sums A, B, Wsum of the label of the corner's vertex.
-//   Both group the lanes of a wave by destination with ballots, as cs_sums of ../meshsimplify/meshsimplify.hip does: a group of
-//   FOLD_MIN lanes or more is summed across the wave and added by one lane (the corners of neighbouring faces land on one
-//   cluster, which would otherwise serialise up to 64 adds per instruction on one address), a smaller group adds lane by lane.
+//   Both bin vertices with the cell_of of ../mesh_cells.h, the one the clustering of ../meshsimplify/meshsimplify.hip used, and
+//   group the lanes of a wave by destination with add_by_label of ../mesh_labels.h, as its cs_sums does: a group of FOLD_MIN lanes
+//   or more is summed across the wave and added by one lane (the corners of neighbouring faces land on one cluster, which would
+//   otherwise serialise up to 64 adds per instruction on one address), a smaller group adds lane by lane.
 // ngp_meshquadric_sums:
 //   mq_export        the sums of every leader, zeros elsewhere.
 // ngp_meshquadric_place:
@@ -21,75 +22,20 @@
 
 #include "../../../include/ngp_meshquadric.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
 
+#include "../mesh_host.h"
+#include "../mesh_cells.h"
+#include "../mesh_labels.h"
+
 constexpr int THREADS = 256;
-constexpr float QF = 1048576.0f;                        // the header's Q
-constexpr double QD = 1048576.0;
 constexpr double SD = 16777216.0;                       // the header's S
 constexpr double W_MAX = 16.0;
 constexpr double EPS = 0.0009765625;                    // 2^-10
 constexpr int SUMS = NGP_MESHQUADRIC_SUMS;              // per label: n, P[3], A[6], B[3], Wsum
 constexpr int CORNER_SUMS = 10;                         // A[6], B[3], Wsum: sums 4..13
-constexpr int FOLD_MIN = 8;                             // lanes of one label from which the wave sums before it adds
-constexpr float CELLS = 2097152.0f;                     // 2^21 cells per axis
 
 typedef unsigned long long u64;
-
-struct Grid {
-    float o[3], cell;
-};
-
-__device__ inline Grid load_grid(const float* __restrict__ origin, float cell) { return Grid{{origin[0], origin[1], origin[2]}, cell}; }
-
-// "cell of a vertex" of ngp_meshsimplify.h: false when outside the grid
-__device__ inline bool cell_of(const Grid& g, const float* __restrict__ x, int c[3], long long q[3]) {
-    bool inside = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float t = (x[k] - g.o[k]) / g.cell;
-        const float fl = floorf(t);
-        const bool ok = fabsf(t) < __uint_as_float(0x7F800000u) && fl >= 0.f && fl < CELLS;    // false for NaN
-        inside = inside && ok;
-        c[k] = ok ? (int)fl : 0;
-        q[k] = ok ? (long long)rintf((t - (float)c[k]) * QF) : 0;
-    }
-    return inside;
-}
-
-__device__ inline long long wave_sum(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-// Adds val[0..N) of every lane with l >= 0 to sums[SUMS * l + first + i].  Wave-uniform: every lane of the wave calls it.
-template <int N>
-__device__ inline void add_by_label(int l, const long long (&val)[N], u64* sums, int first_sum) {
-    const int lane = threadIdx.x & 63;
-    u64 todo = __ballot(l >= 0);
-    while (todo) {                                      // over the distinct labels present
-        const int first = __ffsll((long long)todo) - 1;
-        const int cur = __shfl(l, first, 64);
-        const bool mine = l == cur;
-        const u64 same = __ballot(mine);
-        u64* dst = sums + (size_t)SUMS * (unsigned)cur + first_sum;
-        if (__popcll(same) >= FOLD_MIN) {
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                const long long t = wave_sum(mine ? val[i] : 0);
-                if (lane == first && t) atomicAdd(dst + i, (u64)t);
-            }
-        } else if (mine) {
-#pragma unroll
-            for (int i = 0; i < N; ++i)
-                if (val[i]) atomicAdd(dst + i, (u64)val[i]);
-        }
-        todo &= ~same;
-    }
-}
 
 __global__ __launch_bounds__(THREADS) void mq_members(const float* __restrict__ vertices, const int* __restrict__ label, long long n_v,
                                                       const float* __restrict__ origin, float cell, u64* sums) {
@@ -108,7 +54,7 @@ __global__ __launch_bounds__(THREADS) void mq_members(const float* __restrict__ 
         else
             l = -1;
     }
-    add_by_label<4>(l, val, sums, 0);
+    add_by_label<4>(l, val, sums, SUMS, 0);
 }
 
 __global__ __launch_bounds__(THREADS) void mq_corners(const float* __restrict__ vertices, const int* __restrict__ faces,
@@ -162,7 +108,7 @@ __global__ __launch_bounds__(THREADS) void mq_corners(const float* __restrict__ 
             }
         }
     }
-    add_by_label<CORNER_SUMS>(l, val, sums, 4);
+    add_by_label<CORNER_SUMS>(l, val, sums, SUMS, 4);
 }
 
 __global__ __launch_bounds__(THREADS) void mq_export(const int* __restrict__ label, long long n_v, const long long* __restrict__ sums,
@@ -229,18 +175,10 @@ __global__ __launch_bounds__(THREADS) void mq_place(const float* __restrict__ ve
     }
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline size_t ws_bytes(long long n_v) {
     const size_t b = align256((size_t)n_v * SUMS * 8);
     return b ? b : 256;
 }
-
-inline long long blocks_of(long long n, int per) { return (n + per - 1) / per; }
-
-inline bool cell_ok(float cell) { return cell > 0.f && cell <= 3.402823466e38f; }
-
-inline int launched() { return (int)hipGetLastError(); }
 
 }  // namespace
 

@@ -8,9 +8,9 @@
 //                    probing, the key claimed by a 64-bit atomicCAS from -1), atomicMin of its index into the slot's leader; the
 //                    slot is parked in vertex_label;
 //   cs_sums          vertex_label = the slot's leader, now final; n, P, N and C of the vertex go to the leader's ten int64 sums.
-//                    The vertices of a wave are grouped by label with ballots: a group of FOLD_MIN lanes or more is summed
-//                    across the wave and added by one lane (a heavy cluster would otherwise serialise 64 adds per instruction
-//                    on one address), a smaller group adds lane by lane.  Leaders are counted, one add per wave.
+//                    The vertices of a wave are grouped by label with the ballots of ../mesh_labels.h: a group of FOLD_MIN lanes
+//                    or more is summed across the wave and added by one lane (a heavy cluster would otherwise serialise 64 adds
+//                    per instruction on one address), a smaller group adds lane by lane.  Leaders are counted, one add per wave.
 // ngp_meshsimplify_count:
 //   sf_face_labels   the label triple of every face, (-1, -1, -1) for one that does not survive;
 //   sf_dedupe_insert a second table whose slots hold a face INDEX (empty = INT32_MAX): a face compares its sorted triple with that
@@ -29,50 +29,18 @@
 
 #include "../../../include/ngp_meshsimplify.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
 
 #include "../mesh_compact.h"
+#include "../mesh_cells.h"
+#include "../mesh_labels.h"
+#include "../mesh_mix.h"
 
-constexpr float QF = 1048576.0f;                        // the header's Q
-constexpr double QD = 1048576.0;
 constexpr int SUMS = 10;                                // per leader: n, P[3], N[3], C[3]
-constexpr int FOLD_MIN = 8;                             // lanes of one label from which the wave sums before it adds
 constexpr long long NO_KEY = -1;
 constexpr int NO_FACE = INT32_MAX;
-constexpr float CELLS = 2097152.0f;                     // 2^21 cells per axis
 
 typedef unsigned long long u64;
-
-__device__ inline u64 mix(u64 x) {                      // splitmix64's finaliser
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-
-struct Grid {
-    float o[3], cell;
-};
-
-__device__ inline Grid load_grid(const float* __restrict__ origin, float cell) { return Grid{{origin[0], origin[1], origin[2]}, cell}; }
-
-// the header's "cell of a vertex": false when outside the grid
-__device__ inline bool cell_of(const Grid& g, const float* __restrict__ x, int c[3], long long q[3]) {
-    bool inside = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float t = (x[k] - g.o[k]) / g.cell;
-        const float fl = floorf(t);
-        const bool ok = fabsf(t) < __uint_as_float(0x7F800000u) && fl >= 0.f && fl < CELLS;    // false for NaN
-        inside = inside && ok;
-        c[k] = ok ? (int)fl : 0;
-        q[k] = ok ? (long long)rintf((t - (float)c[k]) * QF) : 0;
-    }
-    return inside;
-}
 
 __device__ inline long long fixed(float x, float lo) {
     if (x != x) return 0;
@@ -105,18 +73,11 @@ __global__ __launch_bounds__(THREADS) void cs_insert(const float* __restrict__ v
     slot_of[v] = (int)s;
 }
 
-__device__ inline long long wave_sum(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 __global__ __launch_bounds__(THREADS) void cs_sums(const float* __restrict__ vertices, const float* __restrict__ normals,
                                                    const float* __restrict__ colors, long long n_v, const float* __restrict__ origin,
                                                    float cell, const int* __restrict__ leader, int* __restrict__ label, u64* sums,
                                                    u64* n_clusters) {
     const long long v = (long long)blockIdx.x * THREADS + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     int l = -1;
     long long val[SUMS] = {};
     if (v < n_v) {
@@ -136,29 +97,15 @@ __global__ __launch_bounds__(THREADS) void cs_sums(const float* __restrict__ ver
         }
     }
     const u64 leaders = __ballot(l >= 0 && l == (int)v);
-    if (lane == 0 && leaders) atomicAdd(n_clusters, (u64)__popcll(leaders));
-    // wave-uniform loop over the distinct labels present
-    u64 todo = __ballot(l >= 0);
-    while (todo) {
-        const int first = __ffsll((long long)todo) - 1;
-        const int cur = __shfl(l, first, 64);
-        const u64 same = __ballot(l == cur);
+    if ((threadIdx.x & 63) == 0 && leaders) atomicAdd(n_clusters, (u64)__popcll(leaders));
+    // one loop over the labels; the sums of absent normals and colours are skipped outright (kernel-uniform)
+    for_each_label(l, [&](int cur, u64 same, int first) {
         const bool mine = l == cur;
         u64* dst = sums + (size_t)SUMS * (unsigned)cur;
-        if (__popcll(same) >= FOLD_MIN) {
-#pragma unroll
-            for (int i = 0; i < SUMS; ++i) {
-                if ((i >= 4 && i < 7 && !normals) || (i >= 7 && !colors)) continue;
-                const long long t = wave_sum(mine ? val[i] : 0);
-                if (lane == first && t) atomicAdd(dst + i, (u64)t);
-            }
-        } else if (mine) {
-#pragma unroll
-            for (int i = 0; i < SUMS; ++i)
-                if (val[i]) atomicAdd(dst + i, (u64)val[i]);
-        }
-        todo &= ~same;
-    }
+        add_group<4>(mine, same, first, val, dst);
+        if (normals) add_group<3>(mine, same, first, val + 4, dst + 4);
+        if (colors) add_group<3>(mine, same, first, val + 7, dst + 7);
+    });
 }
 
 __device__ inline void sort3(int& a, int& b, int& c) {
@@ -299,8 +246,6 @@ inline SLayout slayout(long long n_v, long long n_f) {
     l.total = l.compact + layout(n_v, n_f).total;
     return l;
 }
-
-inline bool cell_ok(float cell) { return cell > 0.f && cell <= 3.402823466e38f; }
 
 }  // namespace
 

@@ -30,14 +30,15 @@
 
 #include "../../../include/ngp_meshsmooth.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
+
+#include "../mesh_host.h"
+#include "../mesh_mix.h"
+#include "../mesh_scan.h"
 
 constexpr int THREADS = 256;
 constexpr int ITERS = 8;
 constexpr int BLOCK_ITEMS = THREADS * ITERS;            // vertices per block of the scan
-constexpr int SCAN_THREADS = 1024;
 constexpr int LONG_ROW = 32;                            // rows longer than this are summed by the wave
 constexpr float QF = 65536.0f;                          // the header's Q
 constexpr double QD = 65536.0;
@@ -48,14 +49,6 @@ constexpr int INSIDE = 1, BOUNDARY = 2, FREE = 4;
 
 typedef unsigned long long u64;
 constexpr u64 NO_KEY = ~(u64)0;
-
-__device__ inline u64 mix(u64 x) {                      // splitmix64's finaliser
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
 
 // the header's grid state: false when the vertex is outside (q is then 0)
 __device__ inline bool state_of(const float* __restrict__ origin, float cell, const float* __restrict__ x, int q[3]) {
@@ -70,47 +63,6 @@ __device__ inline bool state_of(const float* __restrict__ origin, float cell, co
     }
     if (!inside) q[0] = q[1] = q[2] = 0;
     return inside;
-}
-
-__device__ inline long long wave_sum(long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-// block sum over THREADS threads
-__device__ inline long long block_sum(long long acc, long long* lds4) {
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    long long total = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) total += lds4[w];
-    __syncthreads();
-    return total;
-}
-
-// exclusive prefix of v over the THREADS threads of the block, and the block total
-__device__ inline long long block_exscan(long long v, long long& total, long long* lds4) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    long long x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds4[w] = x;
-    __syncthreads();
-    long long pre = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < THREADS / 64; ++i) {
-        const long long s = lds4[i];
-        pre += i < w ? s : 0;
-        total += s;
-    }
-    __syncthreads();
-    return pre + x - v;
 }
 
 __global__ __launch_bounds__(THREADS) void st_inside(const float* __restrict__ vertices, long long n_v, const float* __restrict__ origin,
@@ -175,7 +127,7 @@ __global__ __launch_bounds__(THREADS) void st_degrees(const u64* __restrict__ ke
             }
         }
     }
-    const long long edges = block_sum(edge, lds4), boundary = block_sum(once, lds4);
+    const long long edges = block_sum<THREADS, long long>(edge, lds4), boundary = block_sum<THREADS, long long>(once, lds4);
     if (threadIdx.x == 0) {
         if (edges) atomicAdd(totals, (u64)edges);
         if (boundary) atomicAdd(totals + 1, (u64)boundary);
@@ -190,7 +142,7 @@ __global__ __launch_bounds__(THREADS) void st_block_sums(const int* __restrict__
         const long long v = base + r * THREADS + threadIdx.x;
         if (v < n_v) acc += degree[v];
     }
-    const long long total = block_sum(acc, lds4);
+    const long long total = block_sum<THREADS>(acc, lds4);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -198,27 +150,8 @@ __global__ __launch_bounds__(THREADS) void st_block_sums(const int* __restrict__
 __global__ __launch_bounds__(SCAN_THREADS) void st_scan_blocks(const long long* __restrict__ sums, long long nb, long long* __restrict__ offsets,
                                                                long long* __restrict__ row_end) {
     __shared__ long long s[2][SCAN_THREADS];
-    const int t = threadIdx.x;
-    const long long per = (nb + SCAN_THREADS - 1) / SCAN_THREADS;
-    const long long b0 = min(nb, t * per), b1 = min(nb, b0 + per);
-    long long mine = 0;
-    for (long long b = b0; b < b1; ++b) mine += sums[b];
-    int cur = 0;
-    s[0][t] = mine;
-    __syncthreads();
-    for (int o = 1; o < SCAN_THREADS; o <<= 1) {        // inclusive Hillis-Steele over the per-thread sums
-        long long a = s[cur][t];
-        if (t >= o) a += s[cur][t - o];
-        s[cur ^ 1][t] = a;
-        cur ^= 1;
-        __syncthreads();
-    }
-    long long off = s[cur][t] - mine;
-    for (long long b = b0; b < b1; ++b) {
-        offsets[b] = off;
-        off += sums[b];
-    }
-    if (t == 0) *row_end = s[cur][SCAN_THREADS - 1];
+    const long long total = scan_array([=](long long b) { return sums[b]; }, nb, offsets, s);
+    if (threadIdx.x == 0) *row_end = total;
 }
 
 __global__ __launch_bounds__(THREADS) void st_rows(const int* __restrict__ degree, long long n_v, const long long* __restrict__ offsets,
@@ -232,7 +165,7 @@ __global__ __launch_bounds__(THREADS) void st_rows(const int* __restrict__ degre
         const long long v = base + r * THREADS + threadIdx.x;
         const int d = v < n_v ? degree[v] : 0;
         long long total;
-        const long long at = carry + block_exscan(d, total, lds4);
+        const long long at = carry + block_exscan<THREADS, long long>(d, total, lds4);
         carry += total;
         if (v >= n_v) continue;
         int m = mark[v] & (INSIDE | BOUNDARY);
@@ -244,7 +177,7 @@ __global__ __launch_bounds__(THREADS) void st_rows(const int* __restrict__ degre
         n_free += (m & FREE) != 0;
         n_boundary += (m & BOUNDARY) != 0;
     }
-    const long long tf = block_sum(n_free, lds4), tb = block_sum(n_boundary, lds4);
+    const long long tf = block_sum<THREADS, long long>(n_free, lds4), tb = block_sum<THREADS, long long>(n_boundary, lds4);
     if (threadIdx.x == 0) {
         if (tf) atomicAdd(totals + 2, (u64)tf);
         if (tb) atomicAdd(totals + 3, (u64)tb);
@@ -389,12 +322,6 @@ __global__ __launch_bounds__(THREADS) void nm_finish(const long long* __restrict
     normal[3 * v + 2] = len == 0.0 ? 0.f : (float)(n2 / len);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-inline bool sizes_ok(int64_t n_v, int64_t n_f) { return n_v >= 0 && n_f >= 0 && n_v <= INT32_MAX && n_f <= INT32_MAX; }
-
-inline long long blocks_of(long long n, long long per) { return (n + per - 1) / per; }
-
 // the power of two >= 6 n_f (twice the 3 n_f sides a mesh can have), at least 64
 inline size_t table_slots(long long n_f) {
     size_t t = 64;
@@ -428,11 +355,7 @@ inline Layout layout(long long n_v, long long n_f) {
     return l;
 }
 
-inline bool cell_ok(float cell) { return cell > 0.f && cell <= 3.402823466e38f; }
-
 inline bool factor_ok(float f) { return f >= -1.f && f <= 1.f; }          // false for NaN
-
-inline int launched() { return (int)hipGetLastError(); }
 
 }  // namespace
 

@@ -20,9 +20,9 @@
 
 #include "../../../include/ngp_meshtex.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
+
+#include "../mesh_host.h"
 
 constexpr int THREADS = 256;
 constexpr int MAX_WH = 16384;
@@ -54,10 +54,6 @@ inline int atlas_layout(int64_t n_faces, int texels, Atlas& a) {
     }
     return NGP_ERANGE;
 }
-
-inline long long blocks_of(long long n, int per) { return (n + per - 1) / per; }
-
-inline int launched() { return (int)hipGetLastError(); }
 
 inline bool finite3(const float* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 

@@ -14,9 +14,9 @@
 
 #include "../../../include/ngp_meshtsdf.h"
 
-#define NGP_API extern "C" __attribute__((visibility("default")))
-
 namespace {
+
+#include "../mesh_host.h"
 
 constexpr int THREADS = 256;
 constexpr int CAM_TILE = 128;                           // cameras per LDS tile: 12 floats each
@@ -129,8 +129,6 @@ bool geom_ok(const Dims& d, const float* b6, Geom& g) {
     }
     return true;
 }
-
-inline int launched() { return (int)hipGetLastError(); }
 
 }  // namespace
 

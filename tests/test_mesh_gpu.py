@@ -31,9 +31,10 @@ def gpu_mc(vol, thr, lo, hi):
     return m.vertices.cpu().numpy(), m.faces.cpu().numpy(), m.normals.cpu().numpy()
 
 
-@pytest.mark.parametrize("shape,seed", [((48, 48, 48), 0), ((72, 56, 40), 1), ((33, 65, 17), 2)])
+@pytest.mark.parametrize("shape,seed", [((48, 48, 48), 0), ((72, 56, 40), 1), ((33, 65, 17), 2), ((130, 128, 128), 3)])
 def test_exact_against_numpy_restatement(shape, seed):
-    """(nz, ny, nx) = (72, 56, 40) is the non-cubic 40 x 56 x 72 lattice."""
+    """(nz, ny, nx) = (72, 56, 40) is the non-cubic 40 x 56 x 72 lattice.  (130, 128, 128) has 1040 bricks of 2048 points: the
+    one-workgroup scan of the brick counts takes a second brick per thread."""
     vol = smooth_volume(shape, seed)
     lo, hi = (-0.3, -0.5, 0.1), (0.7, 0.25, 1.3)
     v, f, n = gpu_mc(vol, 0.6, lo, hi)

@@ -106,9 +106,11 @@ def test_build_links_the_thirteenth_library_with_contraction_off():
     assert build.ARCH == "gfx950" and build.MESHATLAS_SOURCES == [os.path.join("meshatlas", "meshatlas.hip")]
     for rel in build.MESHATLAS_SOURCES + build.MESHATLAS_HEADERS:
         assert os.path.exists(os.path.join(build.CSRC, rel)), rel
-    # no ABI header or source of the uniform atlas's library is compiled into this one: only the shared camera and raster device code
+    # no ABI header or source of the uniform atlas's library is compiled into this one: only the shared camera and raster device code,
+    # the integer scans and the host helpers every mesh library shares
     source = open(os.path.join(build.CSRC, build.MESHATLAS_SOURCES[0])).read()
-    assert set(re.findall(r'#include\s*"([^"]+)"', source)) == {"ngp_meshatlas.h", "../mesh_camera.h", "../mesh_raster.h"}
+    assert set(re.findall(r'#include\s*"([^"]+)"', source)) == {"ngp_meshatlas.h", "../mesh_camera.h", "../mesh_raster.h", "../mesh_host.h",
+                                                                 "../mesh_scan.h"}
 
 
 # ---- 2. the layout against hand answers and the restatement

@@ -136,6 +136,19 @@ def test_sizes_and_class_mixes(n_faces, kind):
             mesh.texel_points(m, t, BOX, begin, count)
 
 
+@pytest.mark.parametrize("kind", ["alternate", "all"])
+@pytest.mark.parametrize("n_faces", [64 * 2048, 64 * 2048 + 1])
+def test_classify_where_the_scan_takes_a_second_item_per_thread(n_faces, kind):
+    """64 and 65 blocks of faces times 16 classes are 1024 and 1040 items of the one-workgroup scan: one per thread and two.  The
+    sort alone (no atlas of this size is laid out), the expected values straight from numpy."""
+    cls = mix(kind, n_faces)
+    v, f, n = classed_mesh(cls, 1000 + n_faces)
+    face_class, order, counts = classify(to_mesh(v, f, n))
+    assert np.array_equal(face_class.cpu().numpy(), cls)
+    assert counts.cpu().tolist() == np.bincount(cls, minlength=16).tolist()
+    assert np.array_equal(order.cpu().numpy(), np.argsort(-cls, kind="stable"))
+
+
 # ---- 2. bad input, between canaries
 
 

@@ -206,9 +206,17 @@ def test_every_grid_gives_the_same_words(target, queries):
              mesh.distance_grid(m, cell=float(ext.max()) / 1.9, origin=lo - 0.01 * ext, dims=(2, 3, 5)),
              mesh.distance_grid(m, cell=float(ext.max()) / 9, origin=lo + 0.2 * ext, dims=(2, 3, 5)),      # covers a corner of the target only
              mesh.distance_grid(m, cell=0.31)]
+    # 128, 256 and 258 blocks of 2048 cells for the one-workgroup scan of the block sums: 256 is where its earlier form began a
+    # second chunk.  The target lies inside the first 64 cells along x, so the cells added along x are empty: the same entries.
+    fine = [mesh.distance_grid(m, cell=float(ext.max()) * 1.01 / 64, origin=lo - 0.005 * ext, dims=d) for d in ((64, 64, 64), (128, 64, 64), (129, 64, 64))]
+    assert fine[2].dims == (129, 64, 64) and fine[0].n_entries == fine[1].n_entries == fine[2].n_entries > grids[0].n_entries
     assert grids[0].dims == (1, 1, 1) and grids[1].dims == (2, 3, 5) and grids[0].n_entries == int(R.usable(v, f).sum())
     for grid in grids:
         _same(_run(q, v, f, grid=grid), want)
+    near = ((q >= lo) & (q <= lo + ext)).all(1)                # a query far outside walks every shell of half a million cells
+    assert near.sum() >= 150
+    for grid in fine:
+        _same(_run(q[near], v, f, grid=grid), tuple(w[near] for w in want))
 
 
 def test_permuted_faces_agree_after_mapping_back(target, queries):

@@ -150,6 +150,36 @@ def test_strip_soup_deep_tree_isolated_vertices_and_ties(shuffle_faces):
     assert tets.normals is None and tets.colors is None
 
 
+def pair_soup(n_v=None, n_f=None):
+    """Periods of nine vertices and three faces: two triangles that share an edge (vertices 0-3), an unreferenced vertex, a lone
+    triangle (vertices 5-7), an unreferenced vertex.  Cut to n_f faces, or padded with unreferenced vertices to n_v.  Returns
+    vertices (any bit pattern), faces, and the faces that min_faces=2 keeps: the pairs, by construction."""
+    periods = n_v // 9 if n_f is None else -(-n_f // 3)
+    base = 9 * np.arange(periods, dtype=np.int64)[:, None, None]
+    faces = (base + np.array([[0, 1, 2], [1, 3, 2], [5, 6, 7]])).reshape(-1, 3)[:n_f].astype(np.int32)
+    i = np.arange(len(faces))
+    kept = (i % 3 == 1) | ((i % 3 == 0) & (i + 1 < len(faces)))                 # a pair cut in two is a lone triangle
+    n_v = 9 * periods if n_v is None else n_v
+    v = np.random.RandomState(n_v % 1000).randint(-2 ** 31, 2 ** 31, (n_v, 3), dtype=np.int64).astype(np.int32).view(np.float32)
+    return v, faces, kept
+
+
+@pytest.mark.parametrize("side", ["vertices", "faces"])
+@pytest.mark.parametrize("n", [1024 * 2048, 1024 * 2048 + 1])
+def test_compaction_where_the_scan_takes_a_second_block_per_thread(side, n):
+    """1024 and 1025 blocks of 2048 vertices, then of faces (the other side then has more): the one-workgroup scan of the block
+    counts takes one block per thread, then two.  The expected mesh is a numpy mask and a cumsum."""
+    from ngp_pl_amd import mesh
+    v, f, kept = pair_soup(n_v=n) if side == "vertices" else pair_soup(n_f=n)
+    assert (len(v) if side == "vertices" else len(f)) == n and min(len(v), len(f)) > 300 * 2048
+    used = np.zeros(len(v), bool)
+    used[f[kept]] = True
+    renumber = np.cumsum(used) - 1
+    got = mesh.filter_components(to_mesh(v, f), min_faces=2)
+    assert got.faces.dtype == torch.int32 and np.array_equal(got.faces.cpu().numpy(), renumber[f[kept]])
+    assert np.array_equal(bits(got.vertices), bits(v[used]))
+
+
 def test_filter_invariants():
     from ngp_pl_amd import mesh
     vol = smooth_volume((64, 64, 64), 11)

@@ -85,8 +85,9 @@ def test_code_object_and_build_entry():
     for rel in build.MESHNORMAL_SOURCES + build.MESHNORMAL_HEADERS:
         assert os.path.exists(os.path.join(build.CSRC, rel)), rel
     source = open(os.path.join(build.CSRC, build.MESHNORMAL_SOURCES[0])).read()
-    # no other library's ABI header or source is compiled in: only the walk's device code, shared with libngp_meshdist.so
-    assert set(re.findall(r'#include\s*"([^"]+)"', source)) == {"ngp_meshnormal.h", "../mesh_nearest.h"}
+    # no other library's ABI header or source is compiled in: only the walk's device code, shared with libngp_meshdist.so, and
+    # the host helpers every mesh library shares
+    assert set(re.findall(r'#include\s*"([^"]+)"', source)) == {"ngp_meshnormal.h", "../mesh_nearest.h", "../mesh_host.h"}
     assert "constexpr int THREADS = 256;" in source
 
 

@@ -111,10 +111,10 @@ def test_build_links_the_fourteenth_library_with_contraction_off():
     assert build.ARCH == "gfx950" and build.MESHPHOTO_SOURCES == [os.path.join("meshphoto", "meshphoto.hip")]
     for rel in build.MESHPHOTO_SOURCES + build.MESHPHOTO_HEADERS:
         assert os.path.exists(os.path.join(build.CSRC, rel)), rel
-    # no other library's ABI header or source is compiled into this one (only the shared camera device code), and the tile size the
-    # tests straddle is the kernel's
+    # no other library's ABI header or source is compiled into this one (only the shared camera device code and the host helpers
+    # every mesh library shares), and the tile size the tests straddle is the kernel's
     source = open(os.path.join(build.CSRC, build.MESHPHOTO_SOURCES[0])).read()
-    assert set(re.findall(r'#include\s*"([^"]+)"', source)) == {"ngp_meshphoto.h", "../mesh_camera.h"}
+    assert set(re.findall(r'#include\s*"([^"]+)"', source)) == {"ngp_meshphoto.h", "../mesh_camera.h", "../mesh_host.h"}
     assert "constexpr int CAM_TILE = %d;" % _meshphoto_lib.CAM_TILE in source and PR.CAM_TILE == _meshphoto_lib.CAM_TILE
 
 

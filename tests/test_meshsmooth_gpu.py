@@ -92,6 +92,27 @@ def test_block_and_wave_edges(n):
     check(v3, f3, 1.3, (-1, -1, -1), pin=False)
 
 
+def test_row_scan_takes_a_second_block_per_thread():
+    """699 051 disjoint triangles are 2 097 153 vertices, 1025 blocks of 2048: the one-workgroup scan of the blocks' degree sums
+    takes two blocks per thread.  The row offsets are not an output; a wrong one sends a vertex to another triangle's neighbours,
+    and the pass then moves it elsewhere.  Topology and one pair of passes only: the restatement is slow at this size."""
+    from ngp_pl_amd import mesh
+    n_v = 3 * 699051
+    assert -(-n_v // 2048) == 1025
+    v = np.random.RandomState(7).uniform(-1, 1, (n_v, 3)).astype(np.float32)
+    f = np.arange(n_v, dtype=np.int32).reshape(-1, 3)
+    origin, cell = np.float32([-1.5, -1.5, -1.5]), np.float32(0.01)
+    degree, flags, totals, _ = SR.topology(v, f, origin, cell, False)
+    assert totals.tolist() == [n_v] * 4 and (degree == 2).all()
+    m = to_mesh(v, f)
+    t = mesh.mesh_topology(m, float(cell), origin=origin.tolist(), pin_boundary=False)
+    assert np.array_equal(t.degree.cpu().numpy(), degree) and np.array_equal(t.flags.cpu().numpy(), flags)
+    assert [t.n_edges, t.n_boundary_edges, t.n_free, t.n_boundary_vertices] == totals.tolist()
+    got = mesh.smooth_taubin(m, float(cell), 1, 0.5, -0.53, origin=torch.from_numpy(origin), pin_boundary=False)
+    want = SR.taubin(v, f, origin, cell, 1, 0.5, -0.53, False)
+    assert np.array_equal(bits(got.vertices), bits(want)), "%d position words differ" % (bits(got.vertices) != bits(want)).sum()
+
+
 def fan(n, g, centre):
     """A closed fan of n triangles round a hub with a second ring outside it: the hub has n neighbours, the inner ring's vertices
     5, the outer ring's 4 (and are the boundary).  The hub is the LAST vertex."""
