@@ -38,6 +38,10 @@
                      same way, exactly the brute-force minimum through libngp_meshdist.so's grid; interpolated vertex normals) and
                      the shading of a frame by a rendered normal map behind csrc/meshnormal/ngp_meshnormal.h, which lies beside
                      its sources under csrc/meshnormal/.
+  libngp_meshchart.so -- the texture atlas made of charts (snapped integer corners, a class per face from its integer normal,
+                     union-find over faces that share an edge, shelves of padded rectangles, texel owners by an atomic minimum,
+                     eviction of overlapping faces, dilation, texel points, one UV per vertex and chart) and its renderer behind
+                     csrc/meshchart/ngp_meshchart.h, which lies beside its sources under csrc/meshchart/.
 The mesh libraries share source, each header included inside the including library's anonymous namespace: csrc/mesh_host.h (the
 host helpers of the C entry points, every mesh library), csrc/mesh_scan.h (integer sums and prefix sums over a wave, a workgroup
 and an array), csrc/mesh_labels.h (the lanes of a wave grouped by label), csrc/mesh_cells.h (the clustering grid of the simplifier
@@ -131,6 +135,11 @@ MESHNORMAL_SOURCES = [os.path.join("meshnormal", "meshnormal.hip")]
 MESHNORMAL_HEADERS = ["mesh_host.h", "mesh_nearest.h", os.path.join("meshnormal", "ngp_meshnormal.h")]
 # the orientation test, the closest point of a triangle, the interpolated normal and the shading are the plain f32 expressions of csrc/meshnormal/ngp_meshnormal.h, as tests/mesh_normal_reference.py has them
 MESHNORMAL_CFLAGS = ["-ffp-contract=off"]
+MESHCHART_LIB = os.path.join(CSRC, "libngp_meshchart.so")
+MESHCHART_SOURCES = [os.path.join("meshchart", "meshchart.hip")]
+MESHCHART_HEADERS = ["mesh_host.h", "mesh_scan.h", "mesh_camera.h", "mesh_raster.h", os.path.join("meshchart", "ngp_meshchart.h")]
+# the snap, the f64 quotients, texel points, projection, barycentric weights and the bilinear lookup are the plain expressions of csrc/meshchart/ngp_meshchart.h, as tests/mesh_chart_reference.py has them
+MESHCHART_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -175,8 +184,9 @@ def build(force=False, verbose=False):
     atlas_objs, atlas_jobs = _plan(MESHATLAS_SOURCES, MESHATLAS_HEADERS, lambda src: MESHATLAS_CFLAGS, force)
     photo_objs, photo_jobs = _plan(MESHPHOTO_SOURCES, MESHPHOTO_HEADERS, lambda src: MESHPHOTO_CFLAGS, force)
     normal_objs, normal_jobs = _plan(MESHNORMAL_SOURCES, MESHNORMAL_HEADERS, lambda src: MESHNORMAL_CFLAGS, force)
+    chart_objs, chart_jobs = _plan(MESHCHART_SOURCES, MESHCHART_HEADERS, lambda src: MESHCHART_CFLAGS, force)
     todo = (jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs + dist_jobs
-            + quadric_jobs + decimate_jobs + atlas_jobs + photo_jobs + normal_jobs)
+            + quadric_jobs + decimate_jobs + atlas_jobs + photo_jobs + normal_jobs + chart_jobs)
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -188,7 +198,8 @@ def build(force=False, verbose=False):
                             (MESHTEX_LIB, tex_objs, tex_jobs), (METRICS_LIB, metrics_objs, metrics_jobs),
                             (MESHDIST_LIB, dist_objs, dist_jobs), (MESHQUADRIC_LIB, quadric_objs, quadric_jobs),
                             (MESHDECIMATE_LIB, decimate_objs, decimate_jobs), (MESHATLAS_LIB, atlas_objs, atlas_jobs),
-                            (MESHPHOTO_LIB, photo_objs, photo_jobs), (MESHNORMAL_LIB, normal_objs, normal_jobs)):
+                            (MESHPHOTO_LIB, photo_objs, photo_jobs), (MESHNORMAL_LIB, normal_objs, normal_jobs),
+                            (MESHCHART_LIB, chart_objs, chart_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

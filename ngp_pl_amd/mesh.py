@@ -47,6 +47,10 @@
     m = load_ply("mesh.ply", device="cuda")                        # what save_ply wrote, and nothing else
     save_obj("mesh.obj", m)                                        # mesh.obj + mesh.mtl + mesh.png (needs m.texture with an image)
     save_obj("mesh.obj", m, normal_map=m.normal_map)               # and mesh_normal.png, named by a `norm` line of the MTL
+    t = chart_atlas(m, texel_size=voxel, pad=2)                    # ChartTexture: charts of faces that share a plane class, one UV per vertex and chart (libngp_meshchart.so)
+    m = bake_texture(model, m, texel_size=voxel, charts=True)      # the same bake through the chart atlas; render_textured and compare_renders take it as it is
+    m = extract_mesh(model, 512, decimate=200000, texture=dict(texel_size=1.0, charts=dict(pad=2)))
+    save_glb("mesh.glb", m)                                        # one binary glTF 2.0 file: split vertices, the PNG embedded
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
                               [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]]
@@ -56,10 +60,11 @@
                               [--texture-texels T | --texture-texel-size VOXELS | --texture-max-side N [--texture-min-texels T] [--texture-max-texels T]
                                [--texture-images PHOTOS.npz [--texture-image-bias B] [--texture-image-guard G] [--texture-image-min-cos C]
                                 [--texture-image-power P] [--texture-image-min-views N]]
+                               [--texture-charts [--texture-chart-pad P]]
                                [--texture-normal-map [--texture-normal-max-dist VOXELS] [--texture-normal-two-sided]]
                                [--score-cameras CAMS.npz [--score-out FILE.json]]]
                               [--distance-to REF.ply [--distance-spacing S] [--distance-thresholds T1,T2,...] [--distance-out FILE.json]]
-                              --out mesh.ply | mesh.obj
+                              --out mesh.ply | mesh.obj | mesh.glb
 
 Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
 [k, j, i]; vertices come back in world coordinates.  The reference's notebook (test.ipynb) instead samples
@@ -84,6 +89,7 @@ from . import (_lib, _mesh_lib, _meshcull_lib, _meshdecimate_lib, _meshdist_lib,
 from . import _meshatlas_lib                                      # binds libngp_meshatlas.so only when an AdaptiveTexture is asked for
 from . import _meshphoto_lib                                      # binds libngp_meshphoto.so only when a texture is baked from photographs
 from . import _meshnormal_lib                                     # binds libngp_meshnormal.so only when a normal map is asked for
+from . import _meshchart_lib                                      # binds libngp_meshchart.so only when a ChartTexture is asked for
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -857,6 +863,144 @@ class AdaptiveTexture:
     image: object = None        # (H, W, 3) u8, row 0 on top; None before baking
 
 
+@dataclasses.dataclass
+class ChartTexture:
+    texel_size: float           # world units per texel
+    pad: int                    # texels of dilated border round every chart's rectangle
+    width: int                  # atlas width in texels
+    height: int
+    n_charts: int
+    charts_per_stage: tuple     # charts of stage 0 (all faces), 1 (the faces evicted in 0) and 2 (single faces evicted in 1)
+    evicted_per_stage: tuple    # faces evicted after stages 0 and 1
+    face_chart: object          # (F,) i32: the chart of every face, -1 for a face without a class
+    chart_rects: object         # (n_charts, 6) i32: rectangle origin x, y, size w, h (padding included), plane origin o_u, o_v
+    corner_texels: object       # (F, 3, 2) i32: atlas coordinates of the corners in sixteenths of a texel
+    uvs: object                 # (F, 3, 2) f32: u, v of every face's corners, OBJ's bottom-left origin; one per vertex and chart
+    texel_face: object          # (H, W) i32: the face every texel takes its point from, -1 for none
+    image: object = None        # (H, W, 3) u8, row 0 on top; None before baking
+
+
+def _chart_args(texel_size, pad):
+    """-> (texel_size as a float that is an f32, pad), checked."""
+    if isinstance(texel_size, bool) or not isinstance(texel_size, (int, float, np.integer, np.floating)):
+        raise ValueError("texel_size must be a finite number > 0: %r" % (texel_size,))
+    with np.errstate(all="ignore"):
+        s = float(np.float32(texel_size))
+    if not (math.isfinite(s) and s > 0):
+        raise ValueError("texel_size must be a finite number > 0 (as a float32): %r" % (texel_size,))
+    if isinstance(pad, bool) or not isinstance(pad, (int, np.integer)) or not 0 <= pad <= _meshchart_lib.MAX_PAD:
+        raise ValueError("pad must be an int in 0..%d: %r" % (_meshchart_lib.MAX_PAD, pad))
+    return s, int(pad)
+
+
+def _charts_option(charts):
+    """texture_atlas's `charts`: None or False -> None; True -> pad 2; dict(pad=P) -> P (ValueError for anything else)."""
+    if charts is None or charts is False:
+        return None
+    if charts is True:
+        return 2
+    if not isinstance(charts, dict) or set(charts) - {"pad"}:
+        raise ValueError("charts must be None, True or dict(pad=P): %r" % (charts,))
+    return _chart_args(1.0, charts.get("pad", 2))[1]
+
+
+def chart_atlas(mesh, texel_size, pad=2, return_debug=False):
+    """The atlas of charts of the mesh (csrc/meshchart/ngp_meshchart.h has the exact rule; libngp_meshchart.so): the vertices are
+    snapped to sixteenths of a texel of texel_size world units, every face gets the coordinate plane its integer normal is nearest
+    to, faces of one plane that share an edge form a chart, and every chart is projected onto its plane at one texel per
+    texel_size, inside a rectangle with `pad` texels of border (0..8).  The rectangles go on shelves.  Faces of a chart that overlap
+    another face of it in the projection are taken out and form charts of a second stage, and what overlaps there becomes single
+    faces in a third.  Every texel knows its face (texel_face), the border texels that of the nearest owned texel.  Inside a chart
+    a vertex has one UV.  Returns a ChartTexture without an image after one host read of a count and one of a rectangle array per
+    stage.  All outputs are bit-identical run to run.  return_debug=True also returns dict(face_class (F,) u8, labels: per stage
+    the (F,) i32 chart labels, the smallest face index of the chart of every face the stage labelled and -1 elsewhere)."""
+    s, pad = _chart_args(texel_size, pad)
+    if isinstance(mesh.faces, torch.Tensor) and mesh.faces.dim() == 2 and mesh.faces.shape[0] == 0:
+        raise ValueError("the mesh has no faces: there is nothing to put into an atlas")
+    v, f, _ = _check_mesh(mesh)
+    dev, n_v, n_f = v.device, v.shape[0], f.shape[0]
+    L = _meshchart_lib
+    i32, u8, i64 = torch.int32, torch.uint8, torch.int64
+    face_class = torch.empty(n_f, dtype=u8, device=dev)
+    vf_offsets = torch.empty(n_v + 1, dtype=i64, device=dev)
+    vf_faces = torch.empty(3 * n_f, dtype=i32, device=dev)
+    face_label = torch.empty(n_f, dtype=i32, device=dev)
+    face_chart = torch.full((n_f,), -1, dtype=i32, device=dev)
+    counts = torch.zeros(2, dtype=i64, device=dev)                  # [charts of the stage, faces evicted by the stage before]
+    evicted = torch.empty(n_f, dtype=u8, device=dev)
+    rects = np.zeros((0, 6), np.int32)
+    per_stage, evicted_per_stage, labels = [], [], []
+    W = H = 0
+    owner = None
+    with device_guard(dev):
+        lib = L.lib()
+        ws = torch.empty((lib.ngp_meshchart_classify_workspace_bytes(n_v, n_f) + 7) // 8, dtype=i64, device=dev)
+        L.call("ngp_meshchart_classify", ptr(v), ptr(f), n_v, n_f, s, ptr(face_class), ptr(vf_offsets), ptr(vf_faces), ptr(ws),
+               ws.numel() * 8, stream())
+        ws = torch.empty((lib.ngp_meshchart_label_workspace_bytes(n_f) + 7) // 8, dtype=i64, device=dev)
+        active = (face_class < L.NO_CLASS).to(u8)
+        for stage in range(3):
+            base = rects.shape[0]
+            L.call("ngp_meshchart_label", ptr(f), n_v, n_f, ptr(face_class), ptr(active), ptr(vf_offsets), ptr(vf_faces), int(stage < 2),
+                   base, ptr(face_label), ptr(face_chart), ptr(counts), ptr(ws), ws.numel() * 8, stream())
+            n, gone = counts.cpu().tolist()                         # the stage's one count (with the evictions of the stage before)
+            if stage > 0:
+                evicted_per_stage.append(gone)
+            if n == 0:
+                if stage == 0:
+                    raise ValueError("no face of the mesh has a chart: every face is degenerate, not finite, out of range or larger "
+                                     "than 2^18 texels at texel_size %r" % s)
+                break
+            if return_debug:
+                labels.append(face_label.clone())
+            bounds = torch.empty(n, 4, dtype=i32, device=dev)
+            L.call("ngp_meshchart_bounds", ptr(v), ptr(f), n_v, n_f, s, ptr(face_chart), base, base + n, ptr(bounds), stream())
+            b = bounds.cpu().numpy().astype(np.int64)               # the stage's one rectangle array
+            o = b[:, :2] >> 4
+            sizes = (b[:, 2:] >> 4) - o + 1 + 2 * pad
+            if (sizes > 16384).any():
+                raise ValueError("a chart is wider or higher than 16384 texels: raise texel_size or simplify the mesh")
+            origins, _, W, H = L.pack(sizes, sort=stage < 2, width=W, y0=H)
+            rects = np.concatenate([rects, np.concatenate([origins, sizes, o], 1).astype(np.int32)])
+            chart_rects = torch.from_numpy(rects).to(dev)
+            grown = torch.full((H, W), -1, dtype=i32, device=dev)
+            if owner is not None:
+                grown[:owner.shape[0]] = owner
+            owner = grown
+            placed = (ptr(v), ptr(f), n_v, n_f, s, ptr(face_chart), ptr(chart_rects), rects.shape[0], base, base + n, pad, W, H, ptr(owner))
+            L.call("ngp_meshchart_raster", *placed, stream())
+            per_stage.append(n)
+            if stage == 2:
+                break
+            L.call("ngp_meshchart_evict", *placed, ptr(evicted), ptr(counts[1:]), stream())
+            active, evicted = evicted, (active if stage else torch.empty(n_f, dtype=u8, device=dev))
+        if pad:
+            L.call("ngp_meshchart_dilate", ptr(owner), ptr(torch.empty_like(owner)), W, H, pad, stream())
+        corner_texels = torch.empty(n_f, 3, 2, dtype=i32, device=dev)
+        uvs = torch.empty(n_f, 3, 2, dtype=torch.float32, device=dev)
+        L.call("ngp_meshchart_corners", ptr(v), ptr(f), n_v, n_f, s, ptr(face_chart), ptr(chart_rects), rects.shape[0], pad, W, H,
+               ptr(corner_texels), ptr(uvs), stream())
+    per_stage += [0] * (3 - len(per_stage))
+    evicted_per_stage += [0] * (2 - len(evicted_per_stage))
+    t = ChartTexture(s, pad, W, H, rects.shape[0], tuple(per_stage), tuple(evicted_per_stage), face_chart, chart_rects, corner_texels, uvs,
+                     owner)
+    return (t, dict(face_class=face_class, labels=labels)) if return_debug else t
+
+
+def _check_chart(texture, n_faces, device):
+    """A ChartTexture that belongs to a mesh of n_faces faces on `device` (ValueError otherwise)."""
+    w, h = texture.width, texture.height
+    if not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) and 1 <= x <= 16384 for x in (w, h)):
+        raise ValueError("the texture's size %r x %r is not an atlas's" % (w, h))
+    for name, shape in (("corner_texels", (n_faces, 3, 2)), ("texel_face", (h, w))):
+        t = getattr(texture, name)
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("texture.%s must be a contiguous int32 tensor of shape %r" % (name, shape))
+        _require_cuda(t, "texture." + name)
+        if t.device != device:
+            raise ValueError("texture.%s is on %s, the mesh on %s" % (name, t.device, device))
+
+
 def _texels(texels):
     if isinstance(texels, bool) or not isinstance(texels, (int, np.integer)) or not 1 <= texels <= 256:
         raise ValueError("texels must be an int in 1..256: %r" % (texels,))
@@ -974,14 +1118,23 @@ def fit_texel_size(mesh, max_side, min_texels=1, max_texels=256, probes=24):
     return best
 
 
-def texture_atlas(mesh, texels=8, texel_size=None, min_texels=1, max_texels=256):
+def texture_atlas(mesh, texels=8, texel_size=None, min_texels=1, max_texels=256, charts=None):
     """The atlas layout and the UVs of the mesh's faces (include/ngp_meshtex.h has the exact rule): every face is a right triangle
     with legs of `texels` texel intervals, two faces to a cell of (texels + 5) x (texels + 4) texels with a one-texel extrapolated
     border round each, the cells in rows that make the atlas about square.  Returns a Texture without an image.  No host sync.
     With texel_size (world units per texel interval) every face instead gets the smallest T of the ladder 1, 2, 3, 4, 6, 8, ..., 256
     inside [min_texels, max_texels] at which its longest edge is sampled no coarser than texel_size, the faces are sorted by T and
     every T has a band of cells of its own (csrc/meshatlas/ngp_meshatlas.h has the exact rule; libngp_meshatlas.so): an AdaptiveTexture
-    without an image, after one host read of the 16 class counts.  texels and texel_size exclude each other."""
+    without an image, after one host read of the 16 class counts.  texels and texel_size exclude each other.
+    With charts=True or charts=dict(pad=P), and texel_size, the atlas is chart_atlas(mesh, texel_size, pad) instead, a ChartTexture;
+    texels, min_texels and max_texels must then be left alone."""
+    pad = _charts_option(charts)
+    if pad is not None:
+        if texel_size is None:
+            raise ValueError("charts needs texel_size: world units per texel")
+        if not (isinstance(texels, (int, np.integer)) and not isinstance(texels, bool) and texels == 8) or min_texels != 1 or max_texels != 256:
+            raise ValueError("charts excludes texels, min_texels and max_texels: a chart has one texel size")
+        return chart_atlas(mesh, texel_size, pad)
     if texel_size is not None:
         if not (isinstance(texels, (int, np.integer)) and not isinstance(texels, bool) and texels == 8):
             raise ValueError("texels and texel_size exclude each other: give one of them")
@@ -1013,6 +1166,12 @@ def _texel_points(v, f, normals, texture, b6, begin, count, out=None):
     if out is None:
         out = (torch.empty(count, 3, dtype=torch.float32, device=dev), torch.empty(count, 3, dtype=torch.float32, device=dev),
                torch.empty(count, dtype=torch.uint8, device=dev))
+    if isinstance(texture, ChartTexture):
+        with device_guard(dev):
+            _meshchart_lib.call("ngp_meshchart_texel_points", ptr(v), ptr(f), ptr(normals), v.shape[0], f.shape[0], ptr(texture.corner_texels),
+                                texture.width, texture.height, ptr(texture.texel_face), b6, begin, count, ptr(out[0]), ptr(out[1]),
+                                ptr(out[2]), stream())
+        return out
     if isinstance(texture, AdaptiveTexture):
         with device_guard(dev):
             _meshatlas_lib.call("ngp_meshatlas_texel_points", ptr(v), ptr(f), ptr(normals), v.shape[0], f.shape[0], ptr(texture.order),
@@ -1060,7 +1219,9 @@ def texel_points(mesh, texture, box, begin=0, count=None):
     ((0, 0, 1) where that is zero or not finite), and whether the texel belongs to a face with indices in range and a finite
     point.  mesh.normals must be set.  No host sync."""
     v, f, extra = _check_mesh(mesh)
-    if isinstance(texture, AdaptiveTexture):
+    if isinstance(texture, ChartTexture):
+        _check_chart(texture, f.shape[0], v.device)
+    elif isinstance(texture, AdaptiveTexture):
         _check_adaptive(texture, f.shape[0], v.device)
     else:
         _check_texture(texture, f.shape[0])
@@ -1080,17 +1241,18 @@ def _quantise(c):
 
 
 @torch.no_grad()
-def bake_texture(model, mesh, texels=8, chunk=1 << 20, color_fn=None, box=None, texel_size=None, min_texels=1, max_texels=256):
+def bake_texture(model, mesh, texels=8, chunk=1 << 20, color_fn=None, box=None, texel_size=None, min_texels=1, max_texels=256, charts=None):
     """The mesh with .texture set: texture_atlas(mesh, texels) with the colour of every texel, evaluated `chunk` texels at a time
     at texel_points (inside the model's box; or `box` = (lo3, hi3), needed when model is None) by the model's no-grad forward, as
     vertex_colors uses it, or by color_fn(points (n, 3), dirs (n, 3)) -> (n, 3).  The image stores round(clamp(c, 0, 1) * 255),
     halves to even, and 0 for invalid texels.  If mesh.normals is None the directions come from vertex_normals(mesh).
-    texel_size, min_texels and max_texels are texture_atlas's: with texel_size the texture is an AdaptiveTexture."""
+    texel_size, min_texels, max_texels and charts are texture_atlas's: with texel_size the texture is an AdaptiveTexture, with
+    charts as well a ChartTexture."""
     if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
         raise ValueError("chunk must be an int >= 1: %r" % (chunk,))
     if model is None and (color_fn is None or box is None):
         raise ValueError("without a model both color_fn and box are needed")
-    t = texture_atlas(mesh, texels, texel_size, min_texels, max_texels)
+    t = texture_atlas(mesh, texels, texel_size, min_texels, max_texels, charts)
     v, f, extra = _check_mesh(mesh)
     normals = extra[0] if extra[0] is not None else _normals(v, f)
     b6 = _box6(box if box is not None else _box(model))
@@ -1214,11 +1376,11 @@ def _fill(fill):
 
 @torch.no_grad()
 def bake_texture_from_images(mesh, images, K, poses, img_wh, texels=8, texel_size=None, min_texels=1, max_texels=256, bias=None, guard=1,
-                             min_cos=0.1, power=2, min_views=1, fill=None, model=None, box=None, chunk=1 << 20, return_seen=False):
+                             min_cos=0.1, power=2, min_views=1, fill=None, model=None, box=None, chunk=1 << 20, return_seen=False, charts=None):
     """The mesh with .texture set, as bake_texture leaves it, the colour of every texel blended from the photographs that see it
     (photo_colors at texel_points, `chunk` texels at a time; images, K, poses, img_wh, bias, guard, min_cos, power and min_views are
     photo_colors's, and bias (world units, about two voxels of the lattice the mesh came from) must be given).  texels, or texel_size
-    with min_texels and max_texels, choose the atlas as in texture_atlas.  A valid texel that fewer than min_views photographs see
+    with min_texels and max_texels, or with charts, choose the atlas as in texture_atlas.  A valid texel that fewer than min_views photographs see
     takes the field's colour when `model` is given, evaluated exactly as bake_texture does; otherwise `fill`, three numbers in 0..1
     (default black).  Invalid texels are 0.  The texel points are clamped to the model's box, or to `box` = (lo3, hi3), which is
     needed when model is None.  The image stores round(clamp(c, 0, 1) * 255), halves to even.  If mesh.normals is None the
@@ -1235,7 +1397,7 @@ def bake_texture_from_images(mesh, images, K, poses, img_wh, texels=8, texel_siz
         raise ValueError("without a model a box is needed")
     fill = _fill((0, 0, 0) if fill is None else fill)
     _cameras(K, poses, img_wh)
-    t = texture_atlas(mesh, texels, texel_size, min_texels, max_texels)
+    t = texture_atlas(mesh, texels, texel_size, min_texels, max_texels, charts)
     v, f, extra = _check_mesh(mesh)
     dev = v.device
     Kd, Pd, W, H = _cameras(K, poses, img_wh, dev)
@@ -1333,7 +1495,10 @@ def render_textured(mesh, K, poses, img_wh, background=(1, 1, 1), near=NEAR_DIST
     _cameras(K, poses, img_wh)
     v, f, _ = _check_mesh(mesh)
     adaptive = isinstance(mesh.texture, AdaptiveTexture)
-    if adaptive:
+    chart = isinstance(mesh.texture, ChartTexture)
+    if chart:
+        _check_chart(mesh.texture, f.shape[0], v.device)
+    elif adaptive:
         _check_adaptive(mesh.texture, f.shape[0], v.device)
     else:
         texels = _check_texture(mesh.texture, f.shape[0])
@@ -1358,6 +1523,12 @@ def render_textured(mesh, K, poses, img_wh, background=(1, 1, 1), near=NEAR_DIST
     depth = torch.empty(n_cams, H, W, dtype=torch.float32, device=dev) if return_ids else None
     with device_guard(dev):
         ws = torch.empty(fit, H, W, dtype=torch.int64, device=dev)
+        if chart:
+            t = mesh.texture
+            _meshchart_lib.call("ngp_meshchart_render", ptr(v), ptr(f), v.shape[0], f.shape[0], ptr(t.corner_texels), ptr(img), t.width,
+                                t.height, ptr(Kd), ptr(Pd), n_cams, W, H, near, (C.c_float * 3)(*bg), ptr(ws), ws.numel() * 8, ptr(image),
+                                ptr(ids), ptr(depth), stream())
+            return (image, ids, depth) if return_ids else image
         if adaptive:
             t = mesh.texture
             _meshatlas_lib.call("ngp_meshatlas_render", ptr(v), ptr(f), v.shape[0], f.shape[0], ptr(t.face_place), ptr(img), t.width,
@@ -1676,6 +1847,8 @@ def bake_normal_map(mesh, detail, max_dist, oriented=True, chunk=1 << 20, box=No
         raise ValueError("chunk must be an int >= 1: %r" % (chunk,))
     max_dist = _max_dist(max_dist)
     t = mesh.texture
+    if isinstance(t, ChartTexture):
+        raise ValueError("bake_normal_map does not take a ChartTexture: normal maps on charts are not built yet")
     if not isinstance(t, (Texture, AdaptiveTexture)):
         raise ValueError("bake_normal_map needs mesh.texture (texture_atlas, bake_texture): %r" % (t,))
     v, f, extra = _check_mesh(mesh)
@@ -1894,9 +2067,25 @@ def _texture_options(texture):
     if texture is None:
         return None
     opts = dict(texture) if isinstance(texture, dict) else dict(texels=texture)
-    unknown = set(opts) - {"texels", "texel_size", "max_side", "min_texels", "max_texels", "images", "normal_map"}
+    unknown = set(opts) - {"texels", "texel_size", "max_side", "min_texels", "max_texels", "images", "normal_map", "charts"}
     if unknown:
         raise ValueError("texture: unknown keys %r" % sorted(unknown))
+    if opts.get("charts") not in (None, False):         # the chart atlas: texel_size and the border, nothing else of the atlas options
+        try:
+            pad = _charts_option(opts["charts"])
+        except ValueError as e:
+            raise ValueError("texture: %s" % e)
+        clash = sorted(set(opts) & {"texels", "max_side", "min_texels", "max_texels"})
+        if clash or opts.get("normal_map") not in (None, False):
+            raise ValueError("texture: charts excludes %s" % ", ".join(clash + ["normal_map"] * (opts.get("normal_map") not in (None, False))))
+        if "texel_size" not in opts:
+            raise ValueError("texture: charts needs texel_size (VOXELS per texel)")
+        _chart_args(opts["texel_size"], pad)
+        out = dict(texel_size=float(opts["texel_size"]), charts=dict(pad=pad))
+        if opts.get("images") is not None:
+            out["images"] = _photo_options(opts["images"])
+        return out
+    opts.pop("charts", None)
     if opts.get("normal_map") not in (None, False):     # either atlas with a normal map: the atlas's options with "normal_map" added
         normal = _normal_options(opts.pop("normal_map"))
         out = _texture_options(opts)
@@ -2048,7 +2237,10 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
             size = fit_texel_size(m, texture["max_side"], texture["min_texels"], texture["max_texels"])
         else:
             size = texture["texel_size"] * max((b - a) / (n - 1) for a, b, n in zip(lo, hi, _resolution(resolution)))
-        baked = bake(texel_size=size, min_texels=texture["min_texels"], max_texels=texture["max_texels"])
+        if "charts" in texture:
+            baked = bake(texel_size=size, charts=texture["charts"])
+        else:
+            baked = bake(texel_size=size, min_texels=texture["min_texels"], max_texels=texture["max_texels"])
     elif texture is not None:
         baked = bake(texels=texture)
     normal_map = None
@@ -2107,7 +2299,10 @@ def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=Fals
     the detail mesh is the mesh as it stands just before simplify_voxels / decimate (after the filter and the cull), one of which
     must run; the map is baked where the texture is, before the smoothing; max_dist is given in lattice spacings and defaults to
     max(4, 2 * simplify_voxels), clustering moving a vertex by at most sqrt(3) * simplify_voxels.  The result is then a
-    NormalMappedMesh, a Mesh with one more field, normal_map.  Without it nothing new runs or loads."""
+    NormalMappedMesh, a Mesh with one more field, normal_map.  Without it nothing new runs or loads.
+    texture=dict(texel_size=VOXELS, charts=True) or charts=dict(pad=P) bakes a ChartTexture instead (chart_atlas), with images= if
+    wanted; it excludes texels, max_side, min_texels, max_texels and normal_map.  The chart atlas is laid out on the mesh as it is
+    baked: a later smoothing moves the vertices and keeps the UVs.  Without it nothing new runs or loads."""
     return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels, tsdf, smooth,
                     texture, simplify_placement, decimate)[0]
 
@@ -2255,6 +2450,82 @@ def save_obj(path, m, normal_map=None):
             out.write(_png(normal_image))
 
 
+def glb_vertices(faces, uvs):
+    """The vertex split an indexed format with one UV per vertex needs: (source vertex (N,) int64, uv (N, 2) f32, indices (F, 3)
+    int64) with one output vertex per distinct (vertex index, u bits, v bits), in the order of first use."""
+    f = np.asarray(faces, np.int64).reshape(-1)
+    uv = np.ascontiguousarray(np.asarray(uvs, np.float32).reshape(-1, 2))
+    bits = uv.view(np.uint32).astype(np.int64)
+    key = np.stack([f, bits[:, 0], bits[:, 1]], 1)
+    _, first, inverse = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    rank = np.empty(len(first), np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(len(first))   # unique sorts by key: renumber by first use
+    first = np.sort(first)
+    return f[first], uv[first], rank[inverse.reshape(-1)].reshape(-1, 3)
+
+
+def save_glb(path, m):
+    """One binary glTF 2.0 file of the textured mesh, with numpy and the standard library.  The vertices are split on distinct
+    (vertex index, u bits, v bits) (glb_vertices): a ChartTexture, in which a vertex has one UV per chart, adds only the seam
+    vertices; the per-face atlases give three vertices per face and work all the same.  POSITION with min / max, NORMAL when the
+    mesh has normals, TEXCOORD_0 with v flipped to glTF's top-left origin, u32 indices; the texture's PNG embedded as a buffer
+    view, a linear-mipmap-linear sampler, and a material with baseColorTexture, metallic 0, roughness 1 and KHR_materials_unlit."""
+    import json
+    t = m.texture
+    if t is None or t.image is None:
+        raise ValueError("save_glb needs a baked texture: mesh.texture with an image (bake_texture, extract_mesh(texture=...))")
+    v = _np(m.vertices).astype(np.float32).reshape(-1, 3)
+    f = _np(m.faces).astype(np.int64).reshape(-1, 3)
+    uv = _np(t.uvs).astype(np.float32).reshape(-1, 2)
+    image = np.ascontiguousarray(_np(t.image), np.uint8)
+    if len(uv) != 3 * len(f) or image.shape != (t.height, t.width, 3):
+        raise ValueError("the texture does not belong to this mesh: %d uvs for %d faces, image %r" % (len(uv), len(f), image.shape))
+    if len(f) == 0 or f.min() < 0 or f.max() >= len(v):
+        raise ValueError("save_glb needs faces with indices inside the vertices")
+    src, uv, indices = glb_vertices(f, uv)
+    position = np.ascontiguousarray(v[src])
+    texcoord = np.ascontiguousarray(np.stack([uv[:, 0], np.float32(1) - uv[:, 1]], 1).astype(np.float32))
+    blobs = [indices.astype("<u4").tobytes(), position.astype("<f4").tobytes(), texcoord.astype("<f4").tobytes()]
+    if m.normals is not None:
+        blobs.append(np.ascontiguousarray(_np(m.normals).astype(np.float32).reshape(-1, 3)[src]).astype("<f4").tobytes())
+    blobs.append(_png(image))
+    views, offset, chunks = [], 0, []
+    for k, blob in enumerate(blobs):
+        view = dict(buffer=0, byteOffset=offset, byteLength=len(blob))
+        if k == 0:
+            view["target"] = 34963                       # ELEMENT_ARRAY_BUFFER
+        elif k < len(blobs) - 1:
+            view["target"] = 34962                       # ARRAY_BUFFER
+        views.append(view)
+        blob += b"\x00" * (-len(blob) % 4)
+        chunks.append(blob)
+        offset += len(blob)
+    n = len(src)
+    accessors = [dict(bufferView=0, componentType=5125, count=int(indices.size), type="SCALAR"),
+                 dict(bufferView=1, componentType=5126, count=n, type="VEC3", min=[float(x) for x in position.min(0)],
+                      max=[float(x) for x in position.max(0)]),
+                 dict(bufferView=2, componentType=5126, count=n, type="VEC2")]
+    attributes = dict(POSITION=1, TEXCOORD_0=2)
+    if m.normals is not None:
+        accessors.append(dict(bufferView=3, componentType=5126, count=n, type="VEC3"))
+        attributes["NORMAL"] = 3
+    doc = dict(asset=dict(version="2.0", generator="ngp_pl_amd.mesh"), scene=0, scenes=[dict(nodes=[0])], nodes=[dict(mesh=0)],
+               meshes=[dict(primitives=[dict(attributes=attributes, indices=0, material=0, mode=4)])],
+               materials=[dict(pbrMetallicRoughness=dict(baseColorTexture=dict(index=0), metallicFactor=0.0, roughnessFactor=1.0),
+                               extensions=dict(KHR_materials_unlit={}))],
+               extensionsUsed=["KHR_materials_unlit"], textures=[dict(sampler=0, source=0)],
+               samplers=[dict(magFilter=9729, minFilter=9987, wrapS=33071, wrapT=33071)],
+               images=[dict(bufferView=len(blobs) - 1, mimeType="image/png")], accessors=accessors, bufferViews=views,
+               buffers=[dict(byteLength=offset)])
+    text = json.dumps(doc, separators=(",", ":")).encode("utf-8")
+    text += b" " * (-len(text) % 4)
+    binary = b"".join(chunks)
+    with open(path, "wb") as out:
+        out.write(struct.pack("<4sII", b"glTF", 2, 12 + 8 + len(text) + 8 + len(binary)))
+        out.write(struct.pack("<I4s", len(text), b"JSON") + text)
+        out.write(struct.pack("<I4s", len(binary), b"BIN\x00") + binary)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m ngp_pl_amd.mesh", description="Extract a mesh from a trained checkpoint (binary PLY, or OBJ + MTL + PNG with a texture).")
     ap.add_argument("--ckpt", required=True, help="checkpoint (Lightning .ckpt or a slim state dict)")
@@ -2311,6 +2582,11 @@ def main(argv=None):
                     help="smallest cosine between the normal and the direction to a camera that still counts, in (0, 1] (default 0.1)")
     ap.add_argument("--texture-image-power", type=int, default=None, metavar="P", help="a photograph's weight is that cosine to the power P, 1..8 (default 2)")
     ap.add_argument("--texture-image-min-views", type=int, default=None, metavar="N", help="photographs a texel needs (default 1)")
+    ap.add_argument("--texture-charts", action="store_true",
+                    help="with --texture-texel-size: the atlas of charts instead (faces of one plane class that share an edge lie "
+                         "together, one UV per vertex and chart; VOXELS is then the size of every texel); excludes --texture-texels, "
+                         "--texture-max-side, --texture-min-texels, --texture-max-texels and --texture-normal-map")
+    ap.add_argument("--texture-chart-pad", type=int, default=None, metavar="P", help="texels of border round every chart, 0..8 (default 2)")
     ap.add_argument("--texture-normal-map", action="store_true",
                     help="also bake an object-space normal map from the mesh as it stands before --simplify-voxels / --decimate-* (one of "
                          "which is needed) onto the atlas: NAME_normal.png, named by a `norm` line of the MTL; needs one of the --texture-* "
@@ -2329,7 +2605,8 @@ def main(argv=None):
     ap.add_argument("--distance-spacing", type=float, default=None, metavar="S", help="sample spacing (default: the smaller mean edge length)")
     ap.add_argument("--distance-thresholds", default=None, metavar="T1,T2,...", help="up to 8 distances for precision, recall and F-score")
     ap.add_argument("--distance-out", default=None, metavar="FILE.json", help="also write the record of --distance-to to this file")
-    ap.add_argument("--out", required=True, help="output .ply, or .obj (written with its .mtl and .png; needs --texture-texels)")
+    ap.add_argument("--out", required=True, help="output .ply, or .obj (written with its .mtl and .png; needs --texture-texels), or .glb "
+                                                 "(one binary glTF file with the texture inside; takes what .obj takes)")
     a = ap.parse_args(argv)
     if len(a.resolution) not in (1, 3):
         ap.error("--resolution takes N or nx ny nz")
@@ -2350,7 +2627,21 @@ def main(argv=None):
     for flag, x in (("--smooth-lambda", a.smooth_lambda), ("--smooth-mu", a.smooth_mu)):
         if not (math.isfinite(x) and abs(x) <= 1):
             ap.error("%s takes a finite factor of magnitude <= 1" % flag)
-    obj = a.out.lower().endswith(".obj")
+    glb = a.out.lower().endswith(".glb")
+    obj = a.out.lower().endswith(".obj") or glb          # the outputs that carry a texture
+    if a.texture_chart_pad is not None and not a.texture_charts:
+        ap.error("--texture-chart-pad needs --texture-charts")
+    if a.texture_charts:
+        if a.texture_texel_size is None:
+            ap.error("--texture-charts needs --texture-texel-size VOXELS")
+        if (a.texture_texels is not None or a.texture_max_side is not None or a.texture_min_texels is not None
+                or a.texture_max_texels is not None or a.texture_normal_map):
+            ap.error("--texture-charts excludes --texture-texels, --texture-max-side, --texture-min-texels, --texture-max-texels and "
+                     "--texture-normal-map")
+        if a.texture_chart_pad is not None and not 0 <= a.texture_chart_pad <= _meshchart_lib.MAX_PAD:
+            ap.error("--texture-chart-pad takes P in 0..%d" % _meshchart_lib.MAX_PAD)
+    if glb and a.texture_normal_map:
+        ap.error("--texture-normal-map needs an --out that ends in .obj: the .glb output carries no normal map")
     adaptive = a.texture_texel_size is not None or a.texture_max_side is not None
     if adaptive and a.texture_texels is not None:
         ap.error("--texture-texel-size and --texture-max-side exclude --texture-texels")
@@ -2370,6 +2661,8 @@ def main(argv=None):
     texture_opts = a.texture_texels
     if a.texture_texel_size is not None:
         texture_opts = dict(texel_size=a.texture_texel_size, min_texels=lo_t, max_texels=hi_t)
+        if a.texture_charts:
+            texture_opts = dict(texel_size=a.texture_texel_size, charts=dict(pad=2 if a.texture_chart_pad is None else a.texture_chart_pad))
     elif a.texture_max_side is not None:
         texture_opts = dict(max_side=a.texture_max_side, min_texels=lo_t, max_texels=hi_t)
     if a.texture_texels is not None and not obj:
@@ -2458,7 +2751,9 @@ def main(argv=None):
     m, found, culled, simplified, smoothed = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull,
                                                       a.simplify_voxels, tsdf, smooth, texture_opts, a.simplify_placement or "mean",
                                                       decimate_opts, stats)
-    if obj:
+    if glb:
+        save_glb(a.out, m)
+    elif obj:
         save_obj(a.out, m, normal_map=stats.get("texture_normal_map"))
     else:
         save_ply(a.out, m)
@@ -2479,6 +2774,11 @@ def main(argv=None):
         if isinstance(m.texture, AdaptiveTexture):
             line += ", texel size %.6g, faces per texels %s" % (
                 m.texture.texel_size, " ".join("%d:%d" % (t, n) for t, n in zip(_meshatlas_lib.LADDER, m.texture.counts) if n))
+        if isinstance(m.texture, ChartTexture):
+            owned = float((m.texture.texel_face >= 0).float().mean().item())
+            line += ", texel size %.6g, charts per stage %s, evicted faces %s, %.1f%% of the texels filled" % (
+                m.texture.texel_size, " ".join("%d" % n for n in m.texture.charts_per_stage),
+                " ".join("%d" % n for n in m.texture.evicted_per_stage), 100.0 * owned)
     print(line)
     seen_record = None
     if "texture_images" in stats:
