@@ -42,6 +42,11 @@
                      union-find over faces that share an edge, shelves of padded rectangles, texel owners by an atomic minimum,
                      eviction of overlapping faces, dilation, texel points, one UV per vertex and chart) and its renderer behind
                      csrc/meshchart/ngp_meshchart.h, which lies beside its sources under csrc/meshchart/.
+  libngp_meshsparse.so -- marching cubes over the 8^3-point bricks of the lattice that touch occupied cells of the occupancy grid
+                     (the mask from the bitfield in f64, its dilation, slot lists through the shared scans, the points of the sampled
+                     bricks, one workgroup per brick over a sigma tile in LDS) behind csrc/meshsparse/ngp_meshsparse.h, which lies
+                     beside its sources under csrc/meshsparse/.  csrc/mesh_mc.h holds the per-point and per-cell rules of marching
+                     cubes for this library and libngp_mesh.so, so that both give the same bits.
 The mesh libraries share source, each header included inside the including library's anonymous namespace: csrc/mesh_host.h (the
 host helpers of the C entry points, every mesh library), csrc/mesh_scan.h (integer sums and prefix sums over a wave, a workgroup
 and an array), csrc/mesh_labels.h (the lanes of a wave grouped by label), csrc/mesh_cells.h (the clustering grid of the simplifier
@@ -69,7 +74,7 @@ CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=
 EXTRA = {"mlp.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 MESH_LIB = os.path.join(CSRC, "libngp_mesh.so")
 MESH_SOURCES = [os.path.join("mesh", "mesh.hip")]
-MESH_HEADERS = ["mesh_host.h", "mesh_scan.h", os.path.join("mesh", "mc_tables.h"), os.path.join("..", "..", "include", "ngp_mesh.h")]
+MESH_HEADERS = ["mesh_host.h", "mesh_scan.h", "mesh_mc.h", os.path.join("mesh", "mc_tables.h"), os.path.join("..", "..", "include", "ngp_mesh.h")]
 # positions and normals are the plain f32 expressions of include/ngp_mesh.h (no fused multiply-add), as tests/mc_reference.py has them
 MESH_CFLAGS = ["-ffp-contract=off"]
 MESHFILTER_LIB = os.path.join(CSRC, "libngp_meshfilter.so")
@@ -140,6 +145,11 @@ MESHCHART_SOURCES = [os.path.join("meshchart", "meshchart.hip")]
 MESHCHART_HEADERS = ["mesh_host.h", "mesh_scan.h", "mesh_camera.h", "mesh_raster.h", os.path.join("meshchart", "ngp_meshchart.h")]
 # the snap, the f64 quotients, texel points, projection, barycentric weights and the bilinear lookup are the plain expressions of csrc/meshchart/ngp_meshchart.h, as tests/mesh_chart_reference.py has them
 MESHCHART_CFLAGS = ["-ffp-contract=off"]
+MESHSPARSE_LIB = os.path.join(CSRC, "libngp_meshsparse.so")
+MESHSPARSE_SOURCES = [os.path.join("meshsparse", "meshsparse.hip")]
+MESHSPARSE_HEADERS = ["mesh_host.h", "mesh_scan.h", "mesh_mc.h", os.path.join("mesh", "mc_tables.h"), os.path.join("meshsparse", "ngp_meshsparse.h")]
+# positions, edge parameters and normals are the plain f32 expressions of include/ngp_mesh.h and the occupancy rule the plain f64 expressions of csrc/meshsparse/ngp_meshsparse.h, as tests/mesh_sparse_reference.py has them
+MESHSPARSE_CFLAGS = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):
@@ -185,8 +195,9 @@ def build(force=False, verbose=False):
     photo_objs, photo_jobs = _plan(MESHPHOTO_SOURCES, MESHPHOTO_HEADERS, lambda src: MESHPHOTO_CFLAGS, force)
     normal_objs, normal_jobs = _plan(MESHNORMAL_SOURCES, MESHNORMAL_HEADERS, lambda src: MESHNORMAL_CFLAGS, force)
     chart_objs, chart_jobs = _plan(MESHCHART_SOURCES, MESHCHART_HEADERS, lambda src: MESHCHART_CFLAGS, force)
+    sparse_objs, sparse_jobs = _plan(MESHSPARSE_SOURCES, MESHSPARSE_HEADERS, lambda src: MESHSPARSE_CFLAGS, force)
     todo = (jobs + mesh_jobs + filter_jobs + cull_jobs + simplify_jobs + tsdf_jobs + smooth_jobs + tex_jobs + metrics_jobs + dist_jobs
-            + quadric_jobs + decimate_jobs + atlas_jobs + photo_jobs + normal_jobs + chart_jobs)
+            + quadric_jobs + decimate_jobs + atlas_jobs + photo_jobs + normal_jobs + chart_jobs + sparse_jobs)
     if todo:
         if verbose:
             print("[ngp_pl_amd.build] compiling %d HIP sources for %s" % (len(todo), ARCH))
@@ -199,7 +210,7 @@ def build(force=False, verbose=False):
                             (MESHDIST_LIB, dist_objs, dist_jobs), (MESHQUADRIC_LIB, quadric_objs, quadric_jobs),
                             (MESHDECIMATE_LIB, decimate_objs, decimate_jobs), (MESHATLAS_LIB, atlas_objs, atlas_jobs),
                             (MESHPHOTO_LIB, photo_objs, photo_jobs), (MESHNORMAL_LIB, normal_objs, normal_jobs),
-                            (MESHCHART_LIB, chart_objs, chart_jobs)):
+                            (MESHCHART_LIB, chart_objs, chart_jobs), (MESHSPARSE_LIB, sparse_objs, sparse_jobs)):
         if force or changed or _stale(lib, o):
             _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + o + ["-o", lib])
             if verbose:

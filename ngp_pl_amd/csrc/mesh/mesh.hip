@@ -24,6 +24,7 @@ namespace {
 
 #include "../mesh_host.h"
 #include "../mesh_scan.h"
+#include "../mesh_mc.h"
 
 constexpr int MC_THREADS = 256;
 constexpr int MC_ITERS = 8;
@@ -60,15 +61,16 @@ __global__ __launch_bounds__(MC_THREADS) void mc_count(const float* __restrict__
         int i, j, k;
         decode(p, d, i, j, k);
         const bool hx = i + 1 < d.nx, hy = j + 1 < d.ny, hz = k + 1 < d.nz;
-        const int in0 = vol[p] > thr;
-        const int inx = hx ? vol[p + 1] > thr : in0;
-        const int iny = hy ? vol[p + d.nx] > thr : in0;
-        const int inz = hz ? vol[p + d.nxny] > thr : in0;
+        const int in0 = mc_inside(vol[p], thr);
+        const int inx = hx ? mc_inside(vol[p + 1], thr) : in0;
+        const int iny = hy ? mc_inside(vol[p + d.nx], thr) : in0;
+        const int inz = hz ? mc_inside(vol[p + d.nxny], thr) : in0;
         const int mask = (inx != in0) | (iny != in0) << 1 | (inz != in0) << 2;
         int tris = 0;
         if (hx && hy && hz) {
-            const int cube = in0 | inx << 1 | iny << 2 | (vol[p + d.nx + 1] > thr) << 3 | inz << 4 | (vol[p + d.nxny + 1] > thr) << 5 |
-                             (vol[p + d.nxny + d.nx] > thr) << 6 | (vol[p + d.nxny + d.nx + 1] > thr) << 7;
+            const int cube = in0 | inx << 1 | iny << 2 | mc_inside(vol[p + d.nx + 1], thr) << 3 | inz << 4 |
+                             mc_inside(vol[p + d.nxny + 1], thr) << 5 | mc_inside(vol[p + d.nxny + d.nx], thr) << 6 |
+                             mc_inside(vol[p + d.nxny + d.nx + 1], thr) << 7;
             tris = NGP_MC_TRI_COUNT[cube];
         }
         flags[p] = (uint8_t)(in0 | mask << 1);
@@ -122,9 +124,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void mc_scan_bricks(const int* __rest
 }
 
 __device__ inline float grad_axis(const float* __restrict__ vol, long long q, int c, int n, long long stride, float h) {
-    if (c == 0) return (vol[q + stride] - vol[q]) / h;
-    if (c == n - 1) return (vol[q] - vol[q - stride]) / h;
-    return (vol[q + stride] - vol[q - stride]) / (2.0f * h);
+    return mc_grad_axis([=](int s) { return vol[q + s * stride]; }, c, n, h);
 }
 
 __device__ inline void gradient(const float* __restrict__ vol, const Dims& d, const Geom& g, long long q, int i, int j, int k,
@@ -157,34 +157,19 @@ __global__ __launch_bounds__(MC_THREADS) void mc_emit_vertices(const float* __re
         float ga[3];
         gradient(vol, d, g, p, idx[0], idx[1], idx[2], ga);
         float pa[3];
-        for (int a = 0; a < 3; ++a) pa[a] = g.lo[a] + (float)idx[a] * g.h[a];
+        for (int a = 0; a < 3; ++a) pa[a] = mc_position(g.lo[a], g.h[a], idx[a]);
         long long vi = v0;
         for (int a = 0; a < 3; ++a) {
             if (!(mask >> a & 1)) continue;
             const long long stride = a == 0 ? 1 : a == 1 ? (long long)d.nx : d.nxny;
             const long long q = p + stride;
             const float sb = vol[q];
-            float t = (thr - sa) / (sb - sa);
-            t = fminf(fmaxf(t, 0.0f), 1.0f);
+            const float t = mc_edge_t(thr, sa, sb);
             int jdx[3] = {idx[0], idx[1], idx[2]};
             jdx[a] += 1;
             float gb[3];
             gradient(vol, d, g, q, jdx[0], jdx[1], jdx[2], gb);
-            if (vi < cap) {
-                float pos[3], gv[3];
-                for (int c = 0; c < 3; ++c) {
-                    const float pb = c == a ? g.lo[c] + (float)jdx[c] * g.h[c] : pa[c];
-                    pos[c] = pa[c] + t * (pb - pa[c]);
-                    gv[c] = ga[c] + t * (gb[c] - ga[c]);
-                }
-                verts[3 * vi] = pos[0];
-                verts[3 * vi + 1] = pos[1];
-                verts[3 * vi + 2] = pos[2];
-                if (normals) {
-                    const float nrm = sqrtf(gv[0] * gv[0] + gv[1] * gv[1] + gv[2] * gv[2]);
-                    for (int c = 0; c < 3; ++c) normals[3 * vi + c] = nrm > 0.0f ? -gv[c] / nrm : 0.0f;
-                }
-            }
+            if (vi < cap) mc_vertex(pa, a, mc_position(g.lo[a], g.h[a], jdx[a]), t, ga, gb, verts + 3 * vi, normals ? normals + 3 * vi : nullptr);
             ++vi;
         }
     }
@@ -217,9 +202,9 @@ __global__ __launch_bounds__(MC_THREADS) void mc_emit_faces(Dims d, const uint8_
         for (int tr = 0; tr < nt; ++tr) {
             if (f0 + tr >= cap) break;
             for (int c = 0; c < 3; ++c) {
-                const int e = NGP_MC_TRIS[cube][3 * tr + c];
-                const long long q = off[NGP_MC_EDGE_CORNERS[e][0]];
-                const int axis = e >> 2;
+                int corner, axis;
+                mc_face_corner(cube, tr, c, corner, axis);
+                const long long q = off[corner];
                 const int before = (flags[q] >> 1) & ((1 << axis) - 1);
                 faces[3 * (f0 + tr) + c] = voff[q] + __popc(before);
             }
@@ -232,7 +217,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_lattice_points(Dims d, Geom g, 
     if (s >= count) return;
     int idx[3];
     decode(begin + s, d, idx[0], idx[1], idx[2]);
-    for (int a = 0; a < 3; ++a) xyz[3 * s + a] = g.lo[a] + (float)idx[a] * g.h[a];
+    for (int a = 0; a < 3; ++a) xyz[3 * s + a] = mc_position(g.lo[a], g.h[a], idx[a]);
 }
 
 bool dims_ok(int nx, int ny, int nz, Dims& d) {

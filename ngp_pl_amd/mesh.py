@@ -51,6 +51,10 @@
     m = bake_texture(model, m, texel_size=voxel, charts=True)      # the same bake through the chart atlas; render_textured and compare_renders take it as it is
     m = extract_mesh(model, 512, decimate=200000, texture=dict(texel_size=1.0, charts=dict(pad=2)))
     save_glb("mesh.glb", m)                                        # one binary glTF 2.0 file: split vertices, the PNG embedded
+    mask = brick_mask_from_occupancy(model, 1024)                  # (nbz, nby, nbx) bool: the 8^3-point bricks that touch occupied cells (libngp_meshsparse.so)
+    sv = sparse_density_volume(model, 1024, mask=mask)             # SparseVolume: sigma on those bricks and their neighbours only
+    m = marching_cubes_sparse(sv, 20.0, bounds=(lo3, hi3))         # the dense mesh restricted to the meshed bricks, bit for bit
+    m = extract_mesh(model, 1024, sparse=True, keep_largest=1)     # the same first stage inside extract_mesh; every later stage unchanged
 
     python -m ngp_pl_amd.mesh --ckpt CKPT --scale 0.5 --resolution 512 --threshold 20 [--colors] [--keep-largest K]
                               [--min-component-faces N] [--cull-cameras CAMS.npz [--cull-min-views N] [--cull-bias B]]
@@ -64,13 +68,15 @@
                                [--texture-normal-map [--texture-normal-max-dist VOXELS] [--texture-normal-two-sided]]
                                [--score-cameras CAMS.npz [--score-out FILE.json]]]
                               [--distance-to REF.ply [--distance-spacing S] [--distance-thresholds T1,T2,...] [--distance-out FILE.json]]
+                              [--sparse [--sparse-margin-voxels M]]
                               --out mesh.ply | mesh.obj | mesh.glb
 
 Lattice point (i, j, k) of an (nx, ny, nz) resolution sits at lo + (i, j, k) * (hi - lo) / (n - 1) and is volume element
 [k, j, i]; vertices come back in world coordinates.  The reference's notebook (test.ipynb) instead samples
 np.meshgrid(x, y, z) with the default 'xy' indexing (its axis 0 is y) and scales index-space vertices by 1/N: a notebook vertex
 u = (u0, u1, u2) is the world point lo + N * (u1, u0, u2) * (hi - lo) / (N - 1) of this API.  The default threshold 20 is the notebook's
-sigma_threshold.  The occupancy grid is not used: every lattice point is evaluated.  There is no CPU path.
+sigma_threshold.  By default the occupancy grid is not used: every lattice point is evaluated; with sparse=True only the bricks
+of the lattice that touch occupied cells are.  There is no CPU path.
 """
 import argparse
 import ctypes as C
@@ -90,6 +96,7 @@ from . import _meshatlas_lib                                      # binds libngp
 from . import _meshphoto_lib                                      # binds libngp_meshphoto.so only when a texture is baked from photographs
 from . import _meshnormal_lib                                     # binds libngp_meshnormal.so only when a normal map is asked for
 from . import _meshchart_lib                                      # binds libngp_meshchart.so only when a ChartTexture is asked for
+from . import _meshsparse_lib                                     # binds libngp_meshsparse.so only when a sparse volume is asked for
 from ._mesh_lib import bounds6, device_guard, ptr, stream
 from .networks import NEAR_DISTANCE
 
@@ -207,6 +214,240 @@ def marching_cubes(vol, threshold=20.0, bounds=None):
         _mesh_lib.call("ngp_mesh_emit", ptr(vol), nx, ny, nz, float(threshold), b6, ptr(ws), ws_bytes, n_v, n_f, ptr(verts), ptr(normals),
                        ptr(faces), s)
     return Mesh(verts, faces, normals)
+
+
+def _brick_dims(resolution):
+    nx, ny, nz = resolution
+    B = _meshsparse_lib.BRICK
+    return (nx + B - 1) // B, (ny + B - 1) // B, (nz + B - 1) // B
+
+
+@torch.no_grad()
+def brick_mask_from_occupancy(model, resolution, bounds=None, margin_voxels=1):
+    """Which 8^3-point bricks of the lattice touch an occupied cell of the model's occupancy grid: (nbz, nby, nbx) bool on the
+    model's device, nb = ceil(n / 8).  A brick is meshed when a cell of density_bitfield that meets the box of the brick's cells,
+    grown by margin_voxels lattice spacings, has its bit set, in the smallest cascade that contains the grown box
+    (csrc/meshsparse/ngp_meshsparse.h has the rule, in f64; it reads the bits the ray marcher reads).
+
+    What this means: a surface of the density inside cells that training marked empty is not extracted.  The renderer never sees
+    those either -- it skips the same cells -- so the sparse mesh is the surface of what is rendered.  The bits are set where the
+    density exceeded the occupancy threshold of training, so a `threshold` of the extraction below that threshold wants a larger
+    margin: the iso-surface then lies further out than the occupied cells."""
+    res = _resolution(resolution)
+    nx, ny, nz = res
+    lo, hi = _bounds(model, bounds)
+    m = float(margin_voxels)
+    if not (math.isfinite(m) and 0 <= m <= 1e6):
+        raise ValueError("margin_voxels must be a finite number >= 0: %r" % (margin_voxels,))
+    bits = model.density_bitfield
+    _require_cuda(bits, "the model")
+    nbx, nby, nbz = _brick_dims(res)
+    if _meshsparse_lib.lib().ngp_meshsparse_index_workspace_bytes(nx, ny, nz) == 0:
+        raise ValueError("resolution %r out of range (each axis 2..65535, at most 2^30 bricks of 8^3 points)" % (res,))
+    mask = torch.empty(nbz, nby, nbx, dtype=torch.uint8, device=bits.device)
+    with device_guard(bits.device):
+        _meshsparse_lib.call("ngp_meshsparse_mask", ptr(bits), int(model.cascades), int(model.grid_size), float(model.scale), nx, ny, nz,
+                             bounds6(lo, hi), m, ptr(mask), stream())
+    return mask.view(torch.bool)
+
+
+@dataclasses.dataclass
+class SparseVolume:
+    """Sigma on the sampled bricks of a lattice.  A brick is 8^3 lattice points; the sampled bricks are the meshed ones and their 26
+    neighbours, so that every cell of a meshed brick and every difference of its normals finds its points."""
+    resolution: tuple           # (nx, ny, nz)
+    mask: object                # (nbz, nby, nbx) bool: the meshed bricks
+    brick_table: object         # (nbz, nby, nbx) i32: a brick's sample slot, -1 where it is not sampled
+    mesh_bricks: object         # (M,) i32: the meshed bricks' numbers (bz*nby + by)*nbx + bx, ascending
+    sample_bricks: object       # (S,) i32: the sampled bricks' numbers, ascending: slot s holds brick sample_bricks[s]
+    pool: object                # (S, 512) f32: sigma of a slot's points by local index (k*8 + j)*8 + i
+
+    @property
+    def n_mesh(self):
+        return self.mesh_bricks.shape[0]
+
+    @property
+    def n_sample(self):
+        return self.sample_bricks.shape[0]
+
+    @property
+    def sampled_share(self):
+        """Pool entries over lattice points (a partial brick counts whole)."""
+        nx, ny, nz = self.resolution
+        return self.n_sample * _meshsparse_lib.BRICK_POINTS / float(nx * ny * nz)
+
+    @classmethod
+    def index(cls, resolution, mask):
+        """The SparseVolume of a (nbz, nby, nbx) bool mask with an empty pool (S, 512): dilation, brick table and the two lists
+        on the device, one host read of the two counts."""
+        res = _resolution(resolution)
+        nx, ny, nz = res
+        nbx, nby, nbz = _brick_dims(res)
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or tuple(mask.shape) != (nbz, nby, nbx):
+            raise ValueError("mask must be a (nbz, nby, nbx) = %r bool tensor" % ((nbz, nby, nbx),))
+        _require_cuda(mask, "mask")
+        h = _meshsparse_lib.lib()
+        ws_bytes = h.ngp_meshsparse_index_workspace_bytes(nx, ny, nz)
+        if ws_bytes == 0:
+            raise ValueError("resolution %r out of range (each axis 2..65535, at most 2^30 bricks of 8^3 points)" % (res,))
+        mask = mask.contiguous()
+        dev = mask.device
+        with device_guard(dev):
+            s = stream()
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            counts = torch.empty(2, dtype=torch.int64, device=dev)
+            _meshsparse_lib.call("ngp_meshsparse_index_count", ptr(mask), nx, ny, nz, ptr(ws), ws_bytes, ptr(counts), s)
+            n_mesh, n_sample = counts.tolist()
+            table = torch.empty(nbz, nby, nbx, dtype=torch.int32, device=dev)
+            mesh_bricks = torch.empty(n_mesh, dtype=torch.int32, device=dev)
+            sample_bricks = torch.empty(n_sample, dtype=torch.int32, device=dev)
+            _meshsparse_lib.call("ngp_meshsparse_index_fill", ptr(mask), nx, ny, nz, ptr(ws), ws_bytes, n_mesh, n_sample, ptr(table),
+                                 ptr(mesh_bricks) if n_mesh else None, ptr(sample_bricks) if n_sample else None, s)
+            pool = torch.empty(n_sample, _meshsparse_lib.BRICK_POINTS, dtype=torch.float32, device=dev)
+        return cls(res, mask, table, mesh_bricks, sample_bricks, pool)
+
+    def _coords(self):
+        """(z, y, x) lattice indices (S, 512) i64 of the pool's entries, clamped to the lattice, and which entries are lattice points."""
+        nx, ny, nz = self.resolution
+        nbx, nby, _ = _brick_dims(self.resolution)
+        b = self.sample_bricks.long().view(-1, 1)
+        l = torch.arange(_meshsparse_lib.BRICK_POINTS, device=b.device).view(1, -1)
+        x, y, z = 8 * (b % nbx) + (l & 7), 8 * ((b // nbx) % nby) + ((l >> 3) & 7), 8 * (b // (nbx * nby)) + (l >> 6)
+        real = (x < nx) & (y < ny) & (z < nz)
+        return z.clamp(max=nz - 1), y.clamp(max=ny - 1), x.clamp(max=nx - 1), real
+
+    @classmethod
+    def from_dense(cls, vol, mask):
+        """The sparse volume of `mask` filled by a gather from a dense (nz, ny, nx) f32 volume."""
+        if not isinstance(vol, torch.Tensor) or vol.dim() != 3 or vol.dtype != torch.float32:
+            raise ValueError("vol must be a (nz, ny, nx) float32 tensor")
+        _require_cuda(vol, "vol")
+        nz, ny, nx = vol.shape
+        sv = cls.index((nx, ny, nz), mask.to(vol.device))
+        z, y, x, _ = sv._coords()
+        sv.pool = vol[z, y, x].contiguous()
+        return sv
+
+    def to_dense(self, fill=0.0):
+        """(nz, ny, nx) f32: the pool scattered back onto the lattice, `fill` at the points that were not sampled."""
+        nx, ny, nz = self.resolution
+        vol = torch.full((nz, ny, nx), float(fill), dtype=torch.float32, device=self.pool.device)
+        z, y, x, real = self._coords()
+        vol[z[real], y[real], x[real]] = self.pool[real]
+        return vol
+
+
+def sparse_lattice_points(svol, bounds, begin=0, count=None):
+    """World coordinates (count * 512, 3) of the points of the sample slots begin .. begin+count-1, as sparse_density_volume samples
+    them: lattice_points at the same lattice indices; a point of a partial brick past the lattice's end repeats the last one."""
+    nx, ny, nz = svol.resolution
+    count = svol.n_sample - begin if count is None else count
+    dev = svol.sample_bricks.device
+    xyz = torch.empty(count * _meshsparse_lib.BRICK_POINTS, 3, dtype=torch.float32, device=dev)
+    with device_guard(dev):
+        _meshsparse_lib.call("ngp_meshsparse_points", nx, ny, nz, bounds6(*bounds), ptr(svol.sample_bricks) if svol.n_sample else None,
+                             svol.n_sample, begin, count, ptr(xyz) if count else None, stream())
+    return xyz
+
+
+@torch.no_grad()
+def sparse_density_volume(model, resolution=512, bounds=None, mask=None, chunk_bricks=1 << 13, margin_voxels=1):
+    """model.density at the points of the sampled bricks only: a SparseVolume.  `mask` (nbz, nby, nbx) bool says which bricks are
+    meshed (None: brick_mask_from_occupancy with margin_voxels).  Each chunk of chunk_bricks sample slots goes through the points
+    kernel, ngp_hashgrid_fwd and ngp_density_fwd, the sigmas straight into the pool."""
+    res = _resolution(resolution)
+    nx, ny, nz = res
+    lo, hi = _bounds(model, bounds)
+    _require_cuda(model.xyz_min, "the model")
+    dev = model.xyz_min.device
+    if mask is None:
+        mask = brick_mask_from_occupancy(model, res, (lo, hi), margin_voxels)
+    sv = SparseVolume.index(res, mask.to(dev))
+    n, P = sv.n_sample, _meshsparse_lib.BRICK_POINTS
+    if n == 0:
+        return sv
+    chunk = int(max(1, min(int(chunk_bricks), n, INT32_MAX // P)))
+    enc = model.xyz_encoder
+    eh = enc._half.get(enc.params)
+    xyz = torch.empty(chunk * P, 3, dtype=torch.float32, device=dev)
+    feats = torch.empty(16, chunk * P, 2, dtype=torch.float16, device=dev)
+    b6 = bounds6(lo, hi)
+    with device_guard(dev):
+        s = stream()
+        for begin in range(0, n, chunk):
+            cnt = min(chunk, n - begin)
+            _meshsparse_lib.call("ngp_meshsparse_points", nx, ny, nz, b6, ptr(sv.sample_bricks), n, begin, cnt, ptr(xyz), s)
+            _lib.call("ngp_hashgrid_fwd", ptr(xyz), ptr(model.xyz_min), ptr(model.xyz_max), ptr(eh[enc.n_mlp:]), C.byref(enc.meta), cnt * P,
+                      ptr(feats), s)
+            _lib.call("ngp_density_fwd", ptr(feats), ptr(eh), cnt * P, sv.pool.data_ptr() + 4 * P * begin, None, s)
+    return sv
+
+
+def marching_cubes_sparse(svol, threshold=20.0, bounds=None, canonical=True, return_keys=False):
+    """marching_cubes restricted to the meshed bricks of a SparseVolume: the faces of the dense mesh whose cell lies in a meshed
+    brick and exactly the vertices they reference, positions and normals bit for bit those of marching_cubes on the same sigmas.
+    canonical=True sorts the vertices by key and the faces stably by cell (torch.sort, on the device), which is the dense numbering
+    restricted to the meshed cells; canonical=False returns the kernels' order, brick by brick.  return_keys=True also returns
+    vertex_key (V,) i64 = 3 * (owning point's linear index) + axis and face_cell (F,) i64 = the linear index of the cell's lowest
+    corner, in the order of the mesh returned.  One host sync (the totals, to size the outputs)."""
+    if not isinstance(svol, SparseVolume):
+        raise ValueError("svol must be a SparseVolume")
+    nx, ny, nz = svol.resolution
+    pool = svol.pool
+    _require_cuda(pool, "svol.pool")
+    if pool.dtype != torch.float32 or tuple(pool.shape) != (svol.n_sample, _meshsparse_lib.BRICK_POINTS) or not pool.is_contiguous():
+        raise ValueError("svol.pool must be a contiguous (n_sample, 512) float32 tensor")
+    if bounds is None:
+        bounds = ((0.0, 0.0, 0.0), (nx - 1.0, ny - 1.0, nz - 1.0))
+    b6 = bounds6(*bounds)
+    dev = pool.device
+    n_mesh, n_sample = svol.n_mesh, svol.n_sample
+    n_v = n_f = 0
+    with device_guard(dev):
+        s = stream()
+        if n_mesh:
+            ws_bytes = _meshsparse_lib.lib().ngp_meshsparse_workspace_bytes(n_mesh, n_sample)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            totals = torch.empty(2, dtype=torch.int64, device=dev)
+            lists = (ptr(svol.brick_table), ptr(svol.mesh_bricks), n_mesh, ptr(svol.sample_bricks), n_sample, ptr(ws), ws_bytes)
+            _meshsparse_lib.call("ngp_meshsparse_count", ptr(pool), nx, ny, nz, float(threshold), ptr(svol.mask), *lists, ptr(totals), s)
+            n_v, n_f = totals.tolist()
+            if n_v > INT32_MAX or n_f > INT32_MAX:
+                raise _lib.NgpError("ngp_meshsparse_count: %d vertices, %d faces: NGP_ERANGE (int32 indices)" % (n_v, n_f))
+        verts = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+        normals = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
+        keys = torch.empty(n_v, dtype=torch.int64, device=dev)
+        cells = torch.empty(n_f, dtype=torch.int64, device=dev)
+        if n_v or n_f:
+            _meshsparse_lib.call("ngp_meshsparse_emit", ptr(pool), nx, ny, nz, float(threshold), b6, *lists, n_v, n_f, ptr(verts), ptr(normals),
+                                 ptr(keys), ptr(faces), ptr(cells), s)
+    if canonical and n_v:
+        keys, order = torch.sort(keys)
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(n_v, device=dev)
+        verts, normals = verts[order], normals[order]
+        cells, forder = torch.sort(cells, stable=True)
+        faces = rank[faces[forder].long()].to(torch.int32)
+    m = Mesh(verts, faces, normals)
+    return (m, keys, cells) if return_keys else m
+
+
+def _sparse_options(sparse):
+    """extract_mesh's `sparse`: None (dense), or dict(mask=None, margin_voxels=1)."""
+    if sparse is None or sparse is False:
+        return None
+    if sparse is True:
+        return dict(mask=None, margin_voxels=1)
+    if not isinstance(sparse, dict):
+        raise ValueError("sparse must be False, True or dict(mask=, margin_voxels=): %r" % (sparse,))
+    unknown = set(sparse) - {"mask", "margin_voxels"}
+    if unknown:
+        raise ValueError("sparse: unknown keys %r" % sorted(unknown))
+    m = sparse.get("margin_voxels", 1)
+    if isinstance(m, bool) or not isinstance(m, (int, float)) or not (math.isfinite(m) and 0 <= m <= 1e6):
+        raise ValueError("sparse: margin_voxels must be a finite number >= 0: %r" % (m,))
+    return dict(mask=sparse.get("mask"), margin_voxels=m)
 
 
 @torch.no_grad()
@@ -2154,7 +2395,7 @@ def _tsdf(model, resolution, lo, hi, K, poses, img_wh, trunc_voxels=4.0, min_opa
 
 
 def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull=None, simplify_voxels=None, tsdf=None,
-             smooth=None, texture=None, simplify_placement="mean", decimate=None, stats=None):
+             smooth=None, texture=None, simplify_placement="mean", decimate=None, stats=None, sparse=None):
     """extract_mesh (with `texture`: baked after the simplification and the colours, before the smoothing), (components found, components kept) when a filter option is set (else None), the number of faces the cull
     dropped when `cull` is set (else None), (V0, V1, F0, F1) around the simplification when simplify_voxels is set (else None), and
     (pairs, the topology's totals (4,) i64 on the device or None) when `smooth` is set (else None).  With `decimate` the tuple of the
@@ -2165,6 +2406,9 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
     smooth = _smooth_options(smooth)
     texture = _texture_options(texture)
     decimate = _decimate_options(decimate)
+    sparse = _sparse_options(sparse)
+    if sparse is not None and tsdf is not None:
+        raise ValueError("sparse and tsdf exclude each other: the TSDF is fused on the dense lattice")
     if simplify_voxels is not None and not (math.isfinite(float(simplify_voxels)) and float(simplify_voxels) > 0):
         raise ValueError("simplify_voxels must be a finite number > 0: %r" % (simplify_voxels,))
     simplify_placement = _placement(simplify_placement, "simplify_placement")
@@ -2178,7 +2422,12 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
         if simplify_voxels is None and decimate is None:
             raise ValueError("texture: normal_map carries the normals across a simplification: it needs simplify_voxels or decimate")
     lo, hi = _bounds(model, bounds)
-    if tsdf is None:
+    if sparse is not None:
+        vol = sparse_density_volume(model, resolution, (lo, hi), **sparse)
+        m = marching_cubes_sparse(vol, threshold, (lo, hi))
+        if stats is not None:
+            stats["sparse"] = dict(meshed_bricks=vol.n_mesh, sampled_bricks=vol.n_sample, sampled_share=vol.sampled_share)
+    elif tsdf is None:
         vol = density_volume(model, resolution, (lo, hi))
         m = marching_cubes(vol, threshold, (lo, hi))
     else:
@@ -2265,7 +2514,7 @@ def _extract(model, resolution, threshold, bounds, colors, keep_largest, min_com
 
 
 def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=False, keep_largest=None, min_component_faces=None, cull=None,
-                 simplify_voxels=None, tsdf=None, smooth=None, texture=None, simplify_placement="mean", decimate=None):
+                 simplify_voxels=None, tsdf=None, smooth=None, texture=None, simplify_placement="mean", decimate=None, sparse=False):
     """density_volume + marching_cubes in the model's world coordinates; keep_largest / min_component_faces filter the components
     (filter_components); cull=dict(K=, poses=, img_wh=, min_views=1, bias=None) then drops the faces none of those cameras sees
     (cull_invisible; bias=None is twice the largest lattice spacing); simplify_voxels=K then merges the vertices of every grid
@@ -2302,9 +2551,14 @@ def extract_mesh(model, resolution=512, threshold=20.0, bounds=None, colors=Fals
     NormalMappedMesh, a Mesh with one more field, normal_map.  Without it nothing new runs or loads.
     texture=dict(texel_size=VOXELS, charts=True) or charts=dict(pad=P) bakes a ChartTexture instead (chart_atlas), with images= if
     wanted; it excludes texels, max_side, min_texels, max_texels and normal_map.  The chart atlas is laid out on the mesh as it is
-    baked: a later smoothing moves the vertices and keeps the UVs.  Without it nothing new runs or loads."""
+    baked: a later smoothing moves the vertices and keeps the UVs.  Without it nothing new runs or loads.
+    sparse=True, or dict(mask=None, margin_voxels=1), replaces the first stage by sparse_density_volume + marching_cubes_sparse: the
+    field is evaluated and the cubes are marched only in the 8^3-point bricks of the lattice that touch occupied cells of the model's
+    occupancy grid (brick_mask_from_occupancy, which says what that leaves out), or in the bricks of `mask` (nbz, nby, nbx) bool.
+    The mesh is the dense one restricted to those bricks, in the dense numbering; the other stages follow unchanged.  It excludes
+    tsdf.  Without it nothing new runs or loads."""
     return _extract(model, resolution, threshold, bounds, colors, keep_largest, min_component_faces, cull, simplify_voxels, tsdf, smooth,
-                    texture, simplify_placement, decimate)[0]
+                    texture, simplify_placement, decimate, sparse=sparse)[0]
 
 
 def _np(a):
@@ -2605,6 +2859,11 @@ def main(argv=None):
     ap.add_argument("--distance-spacing", type=float, default=None, metavar="S", help="sample spacing (default: the smaller mean edge length)")
     ap.add_argument("--distance-thresholds", default=None, metavar="T1,T2,...", help="up to 8 distances for precision, recall and F-score")
     ap.add_argument("--distance-out", default=None, metavar="FILE.json", help="also write the record of --distance-to to this file")
+    ap.add_argument("--sparse", action="store_true",
+                    help="evaluate the field and march the cubes only in the 8^3-point bricks of the lattice that touch occupied cells of "
+                         "the checkpoint's occupancy grid; surfaces in cells training marked empty are left out; excludes --tsdf-cameras")
+    ap.add_argument("--sparse-margin-voxels", type=float, default=None, metavar="M",
+                    help="grow every brick by M lattice spacings before it is tested against the occupancy grid (default 1); needs --sparse")
     ap.add_argument("--out", required=True, help="output .ply, or .obj (written with its .mtl and .png; needs --texture-texels), or .glb "
                                                  "(one binary glTF file with the texture inside; takes what .obj takes)")
     a = ap.parse_args(argv)
@@ -2627,6 +2886,12 @@ def main(argv=None):
     for flag, x in (("--smooth-lambda", a.smooth_lambda), ("--smooth-mu", a.smooth_mu)):
         if not (math.isfinite(x) and abs(x) <= 1):
             ap.error("%s takes a finite factor of magnitude <= 1" % flag)
+    if a.sparse_margin_voxels is not None and not a.sparse:
+        ap.error("--sparse-margin-voxels needs --sparse")
+    if a.sparse_margin_voxels is not None and not (math.isfinite(a.sparse_margin_voxels) and 0 <= a.sparse_margin_voxels <= 1e6):
+        ap.error("--sparse-margin-voxels takes M >= 0")
+    if a.sparse and a.tsdf_cameras is not None:
+        ap.error("--sparse excludes --tsdf-cameras: the TSDF is fused on the dense lattice")
     glb = a.out.lower().endswith(".glb")
     obj = a.out.lower().endswith(".obj") or glb          # the outputs that carry a texture
     if a.texture_chart_pad is not None and not a.texture_charts:
@@ -2750,7 +3015,9 @@ def main(argv=None):
                             normal_map=dict(max_dist=a.texture_normal_max_dist, oriented=not a.texture_normal_two_sided))
     m, found, culled, simplified, smoothed = _extract(model, res, a.threshold, None, a.colors, a.keep_largest, a.min_component_faces, cull,
                                                       a.simplify_voxels, tsdf, smooth, texture_opts, a.simplify_placement or "mean",
-                                                      decimate_opts, stats)
+                                                      decimate_opts, stats,
+                                                      dict(margin_voxels=1 if a.sparse_margin_voxels is None else a.sparse_margin_voxels)
+                                                      if a.sparse else None)
     if glb:
         save_glb(a.out, m)
     elif obj:
@@ -2760,6 +3027,9 @@ def main(argv=None):
     line = "%s: %d vertices, %d faces" % (a.out, m.vertices.shape[0], m.faces.shape[0])
     if tsdf is not None:
         line += ", tsdf from %d cameras" % len(tsdf["poses"])
+    if "sparse" in stats:
+        line += ", %d bricks meshed, %d sampled, %.2f%% of the lattice points sampled" % (
+            stats["sparse"]["meshed_bricks"], stats["sparse"]["sampled_bricks"], 100.0 * stats["sparse"]["sampled_share"])
     if found is not None:
         line += ", %d components found, %d kept" % found
     if culled is not None:
